@@ -8,8 +8,16 @@ read schema add(without stats) + remove. It fits one MI355X, so N=1 runs all of 
 getScanFiles wall time until fully consumed. One timed "step" = one getScanFiles over the table, as
 BenchmarkParallelCheckpointReading.java:110-139 runs it: a fresh scan on the loaded snapshot, host
 read of the projected column chunks, H2D, device decode + reconcile, D2H of the selection and of
-add.size, and the consumer summing add.size over the selected rows. The other regions are reported
-beside it:
+add.size, and the consumer summing add.size over the selected rows.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what that figure needs and no more: the
+table, one engine, one snapshot load, W warm-up steps, K timed steps, the result line. `--dump-outputs
+DIR` adds the last timed step's outputs as .npy files (dump_outputs below; the table is generated from
+a fixed seed, so two builds can be compared file for file). `--full` adds everything else, each in
+runs of its own after or around the timed steps: the CPU baseline (oracle/) with the full-size parity
+check of counters and selection bits, the full-row consumer, the JMH-shaped operation, warm and .crc
+snapshot loads, and the other regions; without it their entries in the result
+line are null:
   device_step       the device half of getScanFiles over inputs already resident in HBM (commit-tail
                     keys + table, page headers, snappy, level/value decode of every projected leaf,
                     URI-canonical key hashes, probe, selection, counters); the roofline is measured
@@ -120,6 +128,51 @@ def pmc_traffic(kernel, rows, compression):
         if e.get("rows") == rows and e.get("compression") == compression and kernel in e.get("kernels", {}):
             return {"bytes": e["kernels"][kernel], "source": "profiles/pmc_traffic.json (%s)" % e.get("profile", "?")}
     return None
+
+
+# ------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step handed its consumer
+# ------------------------------------------------------------------------------------------------
+DUMP_SEED = 20250218
+DUMP_WINDOW = 16384      # rows sampled per batch: 65 batches of C3 give ~1M rows, 12 MB of .npy
+
+
+def dump_sample(b, v, n_selected, size_sum):
+    """One scan-file batch for --dump-outputs: its identity and the consumer's two sums over all of
+    it, plus one window of DUMP_WINDOW consecutive rows (selection bit and add.size of every row in
+    it) at a start drawn from (DUMP_SEED, file index, row offset), i.e. the same rows in every run.
+    The window is copied: the batch's arrays are views that the scan recycles."""
+    import numpy as np
+    w = min(DUMP_WINDOW, b.size)
+    rng = np.random.default_rng([DUMP_SEED, b.file_index + 1, b.row_offset, max(0, b.commit_index + 1)])
+    start = int(rng.integers(0, b.size - w + 1))
+    sel = np.ones(w, np.float32) if b.selection is None else b.selection[start:start + w].astype(np.float32)
+    return ((b.file_index, b.commit_index, b.row_offset), b.size, n_selected, size_sum, start, sel,
+            v[start:start + w].astype(np.float64))
+
+
+def dump_outputs(out_dir, dumped, rank, world):
+    """Writes, in replay order of the batches (commit tail first, then the checkpoint files):
+      counters.npy          float64[5]   the scan's ScanMetrics counters after the step
+      batches.npy           float64[B,7] per batch: file index (-1: commit tail), commit index, row
+                                         offset, rows, selected rows, sum of add.size over the selected
+                                         rows, first row of the sampled window
+      selection_sample.npy  float32[S]   selection bit of every sampled row, batches concatenated
+      add_size_sample.npy   float64[S]   add.size of the same rows (selected or not)
+    Counts, offsets and per-batch sums of the configs here stay below 2^53, so float64 holds them
+    exactly. Ranks of a multi-GPU run write <name>.rank<r>.npy."""
+    import numpy as np
+    counters = dumped[-1]
+    batches = sorted(dumped[:-1], key=lambda d: d[0])
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else ".rank%d" % rank
+    np.save(os.path.join(out_dir, "counters%s.npy" % sfx), np.asarray(counters, np.float64))
+    np.save(os.path.join(out_dir, "batches%s.npy" % sfx),
+            np.asarray([list(d[0]) + [d[1], d[2], d[3], d[4]] for d in batches], np.float64).reshape(-1, 7))
+    np.save(os.path.join(out_dir, "selection_sample%s.npy" % sfx),
+            np.concatenate([d[5] for d in batches]) if batches else np.zeros(0, np.float32))
+    np.save(os.path.join(out_dir, "add_size_sample%s.npy" % sfx),
+            np.concatenate([d[6] for d in batches]) if batches else np.zeros(0, np.float64))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -402,6 +455,14 @@ def main(argv=None):
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--jmh-ops", type=int, default=3,
                     help="timed JMH-shaped operations (engine + forPath + snapshot + getScanFiles consumed)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what stands beside the headline: warm / .crc snapshot loads, the "
+                         "device-only step with per-kernel and roofline figures, the full-row consumer, the JMH "
+                         "operation, the CPU baseline and the full-size parity against it (--device-steps, "
+                         "--full-row-steps, --jmh-ops, --cpu-threads and --no-cpu-baseline apply here)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step's getScanFiles handed its consumer as DIR/<name>.npy "
+                         "(see dump_outputs)")
     args = ap.parse_args(argv)
 
     env_world = int(os.environ.get("WORLD_SIZE", "0") or 0)
@@ -484,14 +545,16 @@ def main(argv=None):
     snap = K.Table.forPath(eng, work).getLatestSnapshot(eng)
     snapshot_cold_ms = (time.perf_counter() - t0) * 1e3
     cold_phases = {k: round(v, 3) for k, v in snap.load_ms.items()}
-    warm = []
-    for _ in range(5):
-        t0 = time.perf_counter()
-        snap = K.Table.forPath(eng, work).getLatestSnapshot(eng)
-        warm.append((time.perf_counter() - t0) * 1e3)
-    snapshot_ms = sorted(warm)[len(warm) // 2]
+    snapshot_ms = None
+    if args.full:
+        warm = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            snap = K.Table.forPath(eng, work).getLatestSnapshot(eng)
+            warm.append((time.perf_counter() - t0) * 1e3)
+        snapshot_ms = sorted(warm)[len(warm) // 2]
     snapshot_crc_ms = None
-    if rank == 0 and (world == 1 or not cfg["shared"]):
+    if args.full and rank == 0 and (world == 1 or not cfg["shared"]):
         # with a Spark-style checksum file at the snapshot version (ChecksumReader.getCRCInfo then
         # answers the P&M pass alone)
         from delta_amd import synth
@@ -545,103 +608,108 @@ def main(argv=None):
             sb = sb.withShard(world, rank, exchange=hash_exchange if a2a else None, owner=owner)
         return sb.build()
 
-    # ---- region 1: the device step over inputs resident in HBM (roofline) ----
-    scan = build_scan(snap)
-    t0 = time.perf_counter()
-    scan.prepare(eng)
-    prepare_s = time.perf_counter() - t0
-    n_ckpt_rows = sum(scan.ckpt.num_rows(i) for i in range(len(scan.ckpt_files))) if scan.ckpt else 0
-    n_tail = int(scan.tail.rows)
-    bytes_read, bytes_written = scan.ckpt.traffic() if scan.ckpt else (0, 0)
-    exchange = None
-    if dist is not None and cfg["shared"] and not a2a and owner is None:
-        from delta_amd import shard
-        meta = [(scan.ckpt_index[fi], scan.ckpt.row_offset(fi), scan.ckpt.num_rows(fi))
-                for fi in range(len(scan.ckpt_files or []))]
-        exchange = shard.SelectionExchange(meta, device="cuda")
-    ex_ms = []
-    merged = None
+    # ---- region 1 (--full): the device step over inputs resident in HBM (roofline) ----
+    n_ckpt_rows = n_tail = None
+    ckpt_files = None
+    if args.full:
+        scan = build_scan(snap)
+        t0 = time.perf_counter()
+        scan.prepare(eng)
+        prepare_s = time.perf_counter() - t0
+        n_ckpt_rows = sum(scan.ckpt.num_rows(i) for i in range(len(scan.ckpt_files))) if scan.ckpt else 0
+        n_tail = int(scan.tail.rows)
+        bytes_read, bytes_written = scan.ckpt.traffic() if scan.ckpt else (0, 0)
+        exchange = None
+        if dist is not None and cfg["shared"] and not a2a and owner is None:
+            from delta_amd import shard
+            meta = [(scan.ckpt_index[fi], scan.ckpt.row_offset(fi), scan.ckpt.num_rows(fi))
+                    for fi in range(len(scan.ckpt_files or []))]
+            exchange = shard.SelectionExchange(meta, device="cuda")
+        ex_ms = []
+        merged = None
 
-    def device_step():
-        nonlocal merged
-        scan.run()
-        scan.sync()
-        if owner is not None:
-            owner_ms.append(dict(owner.ms))
-        if exchange is not None:
-            import ctypes as C
-            import torch
-            torch.cuda.synchronize()
-            te = time.perf_counter()
-            offs = (C.c_int64 * max(1, len(exchange.slots)))(*[off for off, _ in exchange.slots])
+        def device_step():
+            nonlocal merged
+            scan.run()
+            scan.sync()
+            if owner is not None:
+                owner_ms.append(dict(owner.ms))
+            if exchange is not None:
+                import ctypes as C
+                import torch
+                torch.cuda.synchronize()
+                te = time.perf_counter()
+                offs = (C.c_int64 * max(1, len(exchange.slots)))(*[off for off, _ in exchange.slots])
 
-            def write_all(i, dst):
-                if i == 0:   # every file of this rank in one call, straight into the collective buffer
-                    base = exchange.buf.data_ptr()
-                    K.check(K.lib().dk_replay_ckpt_selection_bits_all(scan._rh, C.c_void_p(base), offs, 1))
-            merged = exchange.exchange(scan.tail_metrics.as_tuple(), scan.ckpt_metrics.as_tuple(), write_all)
-            torch.cuda.synchronize()
-            ex_ms.append((time.perf_counter() - te) * 1e3)
+                def write_all(i, dst):
+                    if i == 0:   # every file of this rank in one call, straight into the collective buffer
+                        base = exchange.buf.data_ptr()
+                        K.check(K.lib().dk_replay_ckpt_selection_bits_all(scan._rh, C.c_void_p(base), offs, 1))
+                merged = exchange.exchange(scan.tail_metrics.as_tuple(), scan.ckpt_metrics.as_tuple(), write_all)
+                torch.cuda.synchronize()
+                ex_ms.append((time.perf_counter() - te) * 1e3)
 
-    dsteps = args.device_steps if args.device_steps is not None else args.steps
-    for _ in range(args.warmup):
-        device_step()
-    del a2a_ms[:]
-    device_counters = merged[0] if merged else scan.metrics.as_tuple()
-    if a2a:      # the result stays where it was decoded; the counters of the world, for the report
-        device_counters = tuple(scan.tail_metrics.as_tuple()[i] + v
-                                for i, v in enumerate(sum_over_ranks(scan.ckpt_metrics.as_tuple())))
-    if owner is not None:     # every rank's counters are its share: tail actions it owns + its rows
-        device_counters = tuple(sum_over_ranks(scan.metrics.as_tuple()))
-    del owner_ms[:]
-    barrier()
-    stats0 = scan.kernel_stats()
-    t0 = time.perf_counter()
-    for _ in range(dsteps):
-        device_step()
-    barrier()
-    dev_elapsed = max_over_ranks(time.perf_counter() - t0)
-    a2a_dev = sorted(a2a_ms)[len(a2a_ms) // 2] if a2a_ms else None
-    stats1 = scan.kernel_stats()
-    kern = {}
-    for name, (avg1, c1) in stats1.items():
-        avg0, c0 = stats0.get(name, (0.0, 0))
-        if c1 > c0:
-            kern[name] = (avg1 * c1 - avg0 * c0) / (c1 - c0)
-    step_us = kern.pop("step_total", None)
-    dom = max(kern.items(), key=lambda kv: kv[1]) if kern else ("none", 0.0)
-    step_bytes = bytes_read + bytes_written
-    step_gbs = step_bytes / (step_us * 1e-6) / 1e9 if step_us else None
-    # roofline of the dominant kernel with a byte model (dk_parquet_kernel_traffic):
-    # algorithmic bytes of one launch / its average launch time (HIP events on the replay stream)
-    modelled = [k for k in ("k_snap_frag", "k_tile_decode", "k_string_copy", "k_probe") if k in kern]
-    rk = max(modelled, key=lambda k: kern[k]) if modelled else None
-    # every modelled kernel's own roofline fraction (same byte models, same HIP-event averages)
-    kern_roof = {}
-    for k in modelled:
-        r_, w_ = scan.ckpt.kernel_traffic(k)
-        gbs = (r_ + w_) / (kern[k] * 1e-6) / 1e9
-        kern_roof[k] = dict(us=round(kern[k], 1), algorithmic_bytes=r_ + w_, gbs=round(gbs, 1),
-                            frac=round(gbs / HBM_PEAK_GBS, 4))
-    k_read, k_written = scan.ckpt.kernel_traffic(rk) if rk else (0, 0)
-    k_bytes = k_read + k_written
-    achieved = k_bytes / (kern[rk] * 1e-6) / 1e9 if rk else None
-    pmc = pmc_traffic(rk, n_ckpt_rows, compression) if rk else None
-    ckpt_files = list(scan.ckpt_files)
-    if cfg["shared"] and owner is not None:
-        dev_units = sum_over_ranks([n_ckpt_rows + n_tail])[0]       # each rank parsed its share of the tail
-    elif cfg["shared"]:
-        dev_units = sum_over_ranks([n_ckpt_rows])[0] + n_tail      # the tail is replicated, counted once
-    else:
-        dev_units = sum_over_ranks([n_ckpt_rows + n_tail])[0]
-    scan.close()
+        dsteps = args.device_steps if args.device_steps is not None else args.steps
+        for _ in range(args.warmup):
+            device_step()
+        del a2a_ms[:]
+        device_counters = merged[0] if merged else scan.metrics.as_tuple()
+        if a2a:      # the result stays where it was decoded; the counters of the world, for the report
+            device_counters = tuple(scan.tail_metrics.as_tuple()[i] + v
+                                    for i, v in enumerate(sum_over_ranks(scan.ckpt_metrics.as_tuple())))
+        if owner is not None:     # every rank's counters are its share: tail actions it owns + its rows
+            device_counters = tuple(sum_over_ranks(scan.metrics.as_tuple()))
+        del owner_ms[:]
+        barrier()
+        stats0 = scan.kernel_stats()
+        t0 = time.perf_counter()
+        for _ in range(dsteps):
+            device_step()
+        barrier()
+        dev_elapsed = max_over_ranks(time.perf_counter() - t0)
+        a2a_dev = sorted(a2a_ms)[len(a2a_ms) // 2] if a2a_ms else None
+        stats1 = scan.kernel_stats()
+        kern = {}
+        for name, (avg1, c1) in stats1.items():
+            avg0, c0 = stats0.get(name, (0.0, 0))
+            if c1 > c0:
+                kern[name] = (avg1 * c1 - avg0 * c0) / (c1 - c0)
+        step_us = kern.pop("step_total", None)
+        dom = max(kern.items(), key=lambda kv: kv[1]) if kern else ("none", 0.0)
+        step_bytes = bytes_read + bytes_written
+        step_gbs = step_bytes / (step_us * 1e-6) / 1e9 if step_us else None
+        # roofline of the dominant kernel with a byte model (dk_parquet_kernel_traffic):
+        # algorithmic bytes of one launch / its average launch time (HIP events on the replay stream)
+        modelled = [k for k in ("k_snap_frag", "k_tile_decode", "k_string_copy", "k_probe") if k in kern]
+        rk = max(modelled, key=lambda k: kern[k]) if modelled else None
+        # every modelled kernel's own roofline fraction (same byte models, same HIP-event averages)
+        kern_roof = {}
+        for k in modelled:
+            r_, w_ = scan.ckpt.kernel_traffic(k)
+            gbs = (r_ + w_) / (kern[k] * 1e-6) / 1e9
+            kern_roof[k] = dict(us=round(kern[k], 1), algorithmic_bytes=r_ + w_, gbs=round(gbs, 1),
+                                frac=round(gbs / HBM_PEAK_GBS, 4))
+        k_read, k_written = scan.ckpt.kernel_traffic(rk) if rk else (0, 0)
+        k_bytes = k_read + k_written
+        achieved = k_bytes / (kern[rk] * 1e-6) / 1e9 if rk else None
+        pmc = pmc_traffic(rk, n_ckpt_rows, compression) if rk else None
+        ckpt_files = list(scan.ckpt_files)
+        if cfg["shared"] and owner is not None:
+            dev_units = sum_over_ranks([n_ckpt_rows + n_tail])[0]       # each rank parsed its share of the tail
+        elif cfg["shared"]:
+            dev_units = sum_over_ranks([n_ckpt_rows])[0] + n_tail      # the tail is replicated, counted once
+        else:
+            dev_units = sum_over_ranks([n_ckpt_rows + n_tail])[0]
+        scan.close()
 
     # ---- the headline: getScanFiles until fully consumed ----
     capture = {}
+    shape = {}                  # rows and files of this rank's scan, read off the first step's scan
 
-    def e2e_step(capture_result=False):
+    def e2e_step(capture_result=False, dump=None):
         """One getScanFiles on the loaded snapshot, consumed as the JMH benchmark consumes it
-        (BenchmarkParallelCheckpointReading.java:124-135: sum add.size over the selected rows)."""
+        (BenchmarkParallelCheckpointReading.java:124-135: sum add.size over the selected rows).
+        `dump`: a list that receives dump_sample() of every batch (--dump-outputs, last timed step)."""
         sc = build_scan(snap)
         size_sum, n_sel = 0, 0
         tail_paths, bits = [], []
@@ -659,14 +727,15 @@ def main(argv=None):
             if cprof:
                 t_d = time.perf_counter(); t_v += t_d - t_b
             if b.selection is None:
-                size_sum += int(v.sum())
-                n_sel += b.size
+                s_, k_ = int(v.sum()), b.size
             else:
                 s_, k_ = masked_sum(v, b.selection)
-                size_sum += s_
-                n_sel += k_
+            size_sum += s_
+            n_sel += k_
             if cprof:
                 t_a = time.perf_counter(); t_s += t_a - t_d
+            if dump is not None:
+                dump.append(dump_sample(b, v, k_, s_))
             if capture_result:
                 if b.file_index < 0:
                     pc = b.data["add.path"]
@@ -680,6 +749,11 @@ def main(argv=None):
             else sc.ckpt_metrics.addFilesSeen                  # a replicated tail counts once
         if capture_result:
             capture.update(counters=sc.metrics.as_tuple(), tail_paths=tail_paths, bits=bits)
+        if dump is not None:
+            dump.append(sc.metrics.as_tuple())
+        if not shape:
+            shape.update(n_ckpt_rows=sum(sc.ckpt.num_rows(i) for i in range(len(sc.ckpt_files))) if sc.ckpt else 0,
+                         n_tail=int(sc.tail.rows), ckpt_files=list(sc.ckpt_files or []))
         phases = dict(sc.prepare_ms)
         phases["consume"] = consume_ms
         if cprof:   # DK_CONSUME_PROFILE=1: where the consumer's time goes
@@ -698,15 +772,16 @@ def main(argv=None):
         return seen, n_sel, size_sum, phases
 
     for i in range(args.warmup):
-        e2e_step(capture_result=(i == 0 and world == 1))
+        e2e_step(capture_result=(i == 0 and world == 1 and args.full))     # captured for the parity check
     barrier()
     t0 = time.perf_counter()
     seen_tot = sel_tot = size_tot = 0
     phase_sum = {}
     step_ms = []                                    # each timed step's wall time (this rank)
-    for _ in range(args.steps):
+    dumped = [] if args.dump_outputs else None
+    for i in range(args.steps):
         ts = time.perf_counter()
-        seen, n_sel, size_sum, phases = e2e_step()
+        seen, n_sel, size_sum, phases = e2e_step(dump=dumped if i == args.steps - 1 else None)
         step_ms.append((time.perf_counter() - ts) * 1e3)
         seen_tot += seen
         sel_tot += n_sel
@@ -718,6 +793,10 @@ def main(argv=None):
     seen_all, sel_all, size_all = sum_over_ranks([seen_tot, sel_tot, size_tot])
     value = seen_all / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+    if n_ckpt_rows is None:
+        n_ckpt_rows, n_tail, ckpt_files = shape["n_ckpt_rows"], shape["n_tail"], shape["ckpt_files"]
+    if dumped:
+        dump_outputs(args.dump_outputs, dumped, rank, world)
 
     # ---- beside the headline: a consumer that reads every selected scan file's path, partition
     # values and size (a connector's split planner, MultiThreadedTableReader.java:204-251), not only
@@ -753,7 +832,7 @@ def main(argv=None):
             phases.get("checkpoint_open", 0) + phases.get("device_run", 0)
 
     full_row = None
-    if args.full_row_steps > 0:
+    if args.full and args.full_row_steps > 0:
         full_row_step()                                          # warm-up
         barrier()
         t_f = time.perf_counter()
@@ -775,7 +854,7 @@ def main(argv=None):
     # a new engine, Table.forPath, getLatestSnapshot, getScanState, getScanFiles consumed (sum of
     # add.size), engine closed -- one warm-up op, then --jmh-ops timed ops, average time per op ----
     jmh = None
-    if args.jmh_ops > 0 and world == 1:
+    if args.full and args.jmh_ops > 0 and world == 1:
         def jmh_op():
             t_o = time.perf_counter()
             e2 = K.GpuEngine()
@@ -846,13 +925,8 @@ def main(argv=None):
         "addFilesSeen_per_step": seen_all // args.steps, "selected_per_step": sel_all // args.steps,
         "size_sum_per_step": size_all // args.steps,
         "getScanFiles_phases_ms": {k: round(v / args.steps, 2) for k, v in phase_sum.items()},
-        "device_step": {"ms": dev_elapsed / max(1, dsteps) * 1e3, "steps": dsteps,
-                        "actions_per_s": dev_units * dsteps / dev_elapsed if dev_elapsed else None,
-                        "counters": list(device_counters),
-                        "exchange_ms": (sorted(ex_ms)[len(ex_ms) // 2] if ex_ms else a2a_dev),
-                        "owner_exchange_ms": ({k: round(sorted(m[k] for m in owner_ms)[len(owner_ms) // 2], 3)
-                                               for k in owner_ms[0]} if owner_ms else None),
-                        "prepare_s": prepare_s},
+        "full": args.full,          # without --full the entries below that take runs of their own are null
+        "device_step": None,
         "full_row_consume": full_row,
         "jmh_op": jmh,
         "snapshot_load_ms": snapshot_ms,
@@ -861,23 +935,37 @@ def main(argv=None):
         "snapshot_load_cold_phases_ms": cold_phases,
         "snapshot_load_with_crc_ms": snapshot_crc_ms,
         "snapshot_load_phases_ms": {k: round(v, 3) for k, v in snap.load_ms.items()},
-        "kernels_us": {k: round(v, 2) for k, v in sorted(kern.items(), key=lambda kv: -kv[1])},
-        "kernels_roofline": kern_roof,
-        "roofline": {"bound": "hbm", "kernel": rk, "kernel_us": kern.get(rk),
-                     "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-                     "traffic": pmc["bytes"] if pmc else None,
-                     "traffic_source": pmc["source"] if pmc else None,
-                     "algorithmic_bytes": k_bytes, "algorithmic_read": k_read, "algorithmic_written": k_written,
-                     "dominant_kernel": dom[0], "dominant_kernel_us": dom[1],
-                     "step": {"device_us": step_us, "algorithmic_bytes": step_bytes, "bytes_read": bytes_read,
-                              "bytes_written": bytes_written, "achieved_gbs": step_gbs,
-                              "frac": (step_gbs / HBM_PEAK_GBS) if step_gbs else None}},
+        "kernels_us": None,
+        "kernels_roofline": None,
+        "roofline": None,
     }
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if args.full:
+        result.update({
+            "device_step": {"ms": dev_elapsed / max(1, dsteps) * 1e3, "steps": dsteps,
+                            "actions_per_s": dev_units * dsteps / dev_elapsed if dev_elapsed else None,
+                            "counters": list(device_counters),
+                            "exchange_ms": (sorted(ex_ms)[len(ex_ms) // 2] if ex_ms else a2a_dev),
+                            "owner_exchange_ms": ({k: round(sorted(m[k] for m in owner_ms)[len(owner_ms) // 2], 3)
+                                                   for k in owner_ms[0]} if owner_ms else None),
+                            "prepare_s": prepare_s},
+            "kernels_us": {k: round(v, 2) for k, v in sorted(kern.items(), key=lambda kv: -kv[1])},
+            "kernels_roofline": kern_roof,
+            "roofline": {"bound": "hbm", "kernel": rk, "kernel_us": kern.get(rk),
+                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+                         "traffic": pmc["bytes"] if pmc else None,
+                         "traffic_source": pmc["source"] if pmc else None,
+                         "algorithmic_bytes": k_bytes, "algorithmic_read": k_read, "algorithmic_written": k_written,
+                         "dominant_kernel": dom[0], "dominant_kernel_us": dom[1],
+                         "step": {"device_us": step_us, "algorithmic_bytes": step_bytes, "bytes_read": bytes_read,
+                                  "bytes_written": bytes_written, "achieved_gbs": step_gbs,
+                                  "frac": (step_gbs / HBM_PEAK_GBS) if step_gbs else None}},
+        })
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
         got = (capture["counters"], capture["tail_paths"], capture["bits"]) if capture else None
         aff, quota = cpu_share()
-        # the pool's rule: one GPU's share of the box is 16 CPUs although nproc shows the machine
+        # by default no more threads than the CPU quota, or 16 where there is none (a many-core host
+        # is usually shared)
         threads = args.cpu_threads or min(aff, quota or 16)
         result["cpu_baseline"] = cpu_baseline(work, ckpt_files, cfg, threads, got=got)
         result["cpu_baseline_host"] = {"cpu_count": os.cpu_count(), "nproc": aff, "cgroup_cpus": quota,

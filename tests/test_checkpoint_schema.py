@@ -3,10 +3,11 @@
 Expected field order and nullability are restated from the reference's schema definitions
 (kernel-api/.../internal/actions/: SingleAction.java:30-37, AddFile.java:42-70, RemoveFile.java:23-38,
 DeletionVectorDescriptor.java:84-90, Metadata.java:57-72, Format.java:42-48, Protocol.java:49-54,
-SetTransaction.java:28-32, DomainMetadata.java:34-38). When /root/reference is present the restatement
-is itself checked against the Java text (`.add("name", TYPE, nullable)` lines)."""
+SetTransaction.java:28-32, DomainMetadata.java:34-38). The restatement is itself checked against the
+field lists recorded from the Java text (`.add("name", TYPE, nullable)` lines) by
+tests/golden/make_fixtures.py in tests/golden/checkpoint_schema_fields.json."""
+import json
 import os
-import re
 
 import pytest
 
@@ -60,7 +61,7 @@ _DV_KEYS = ("storageType", "pathOrInlineDv", "offset", "sizeInBytes", "cardinali
 
 
 
-ACT = "/root/reference/kernel/kernel-api/src/main/java/io/delta/kernel/internal/actions"
+FIELDS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "checkpoint_schema_fields.json")
 
 # struct -> [(field, nullable)] in declaration order
 EXPECTED = {
@@ -129,31 +130,13 @@ def test_parquet_repetition_of_written_schema(tmp_path):
     assert rep["protocol.minReaderVersion"] == 1
 
 
-@pytest.mark.skipif(not os.path.isdir(ACT), reason="reference sources not present")
 def test_restatement_matches_reference_java():
+    with open(FIELDS) as f:
+        recorded = json.load(f)
+    assert sorted(recorded) == sorted(JAVA)
     for struct, (fname, const) in JAVA.items():
-        text = open(os.path.join(ACT, fname)).read()
-        at = text.index(const + " =")
-        end = text.index(";", at)
-        body = text[at:end]
-        fields = []
-        for seg in body.split(".add(")[1:]:
-            # top-level arguments of .add(name, type[, nullable]); StructType.add(name, type)
-            # defaults to nullable
-            args, depth, cur = [], 0, ""
-            for ch in seg:
-                if ch == ")" and depth == 0:
-                    break
-                depth += (ch == "(") - (ch == ")")
-                if ch == "," and depth == 0:
-                    args.append(cur)
-                    cur = ""
-                else:
-                    cur += ch
-            args.append(cur)
-            args = [re.sub(r"/\*.*?\*/", "", a).strip() for a in args]
-            name = re.match(r'"(\w+)"', args[0]).group(1)
-            fields.append((name, args[2] == "true" if len(args) > 2 else True))
+        assert (recorded[struct]["file"], recorded[struct]["constant"]) == (fname, const)
+        fields = [(name, nullable) for name, nullable in recorded[struct]["fields"]]
         exp = EXPECTED[struct]
         if struct == "add":
             exp = exp[:-1]            # stats: SCHEMA_WITH_STATS = SCHEMA_WITHOUT_STATS.add(JSON_STATS_FIELD)
