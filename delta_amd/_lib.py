@@ -56,6 +56,10 @@ class dk_read_options(C.Structure):
                 ("window_rows", C.c_int32)]
 
 
+class dk_scan_options(C.Structure):
+    _fields_ = [("compact", C.c_int32), ("batch_rows", C.c_int32), ("window_rows", C.c_int32)]
+
+
 class dk_batch_column(C.Structure):
     _fields_ = [("present", C.c_int32), ("phys", C.c_int32), ("width", C.c_int32), ("max_def", C.c_int32),
                 ("max_rep", C.c_int32), ("rep_def", C.c_int32), ("n_values", C.c_int64), ("value_offset", C.c_int64),
@@ -138,7 +142,8 @@ EXPORTS = ["dk_last_error", "dk_version", "dk_engine_create", "dk_engine_destroy
            "dk_program_free", "dk_json_parse", "dk_parsed_num_leaves", "dk_parsed_leaf_path", "dk_parsed_column_get",
            "dk_parsed_eval", "dk_parsed_free", "dk_comm_unique_id", "dk_comm_create", "dk_comm_create_callbacks",
            "dk_comm_create_local", "dk_comm_world", "dk_comm_rank", "dk_comm_allreduce_i64", "dk_comm_alltoallv",
-           "dk_comm_abort", "dk_comm_last_run", "dk_comm_last_steps", "dk_comm_destroy", "dk_replay_owner_run", "dk_owner_protocol_run"]
+           "dk_comm_abort", "dk_comm_last_run", "dk_comm_last_steps", "dk_comm_destroy", "dk_replay_owner_run", "dk_owner_protocol_run",
+           "dk_replay_scan_open", "dk_scan_next", "dk_scan_stats", "dk_scan_close"]
 
 
 def lib(build_if_missing=True):
@@ -213,6 +218,10 @@ def lib(build_if_missing=True):
         "dk_reader_num_rows": (I64, [P, I32]),
         "dk_batch_release": (None, [C.POINTER(dk_batch)]),
         "dk_reader_close": (None, [P]),
+        "dk_replay_scan_open": (C.c_int, [P, C.POINTER(C.c_char_p), I32, C.POINTER(dk_scan_options), C.POINTER(P)]),
+        "dk_scan_next": (C.c_int, [P, C.POINTER(C.POINTER(dk_batch)), C.POINTER(P)]),
+        "dk_scan_stats": (C.c_int, [P, C.POINTER(I64)]),
+        "dk_scan_close": (None, [P]),
         "dk_dv_load": (C.c_int, [P, C.c_char_p, C.POINTER(dk_dv_descriptor), I32, C.POINTER(P)]),
         "dk_dv_num_bits": (I64, [P, I32]),
         "dk_dv_bitmap": (C.c_int, [P, I32, P, I64, I32]),

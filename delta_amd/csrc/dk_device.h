@@ -160,6 +160,29 @@ struct ArrowWin {
   int32_t* overflow;           // out: set when a rebased offset does not fit int32
 };
 
+// scan-file batch reader (dk_scan_*, compact mode): one leaf's gather of a window of selected rows
+// from the decoded column into the window's Arrow-style buffers (dk_export.hip). `rows` are the
+// window's rows of the file's selected-row list (ascending file rows).
+struct ExportLeaf {
+  // source: the decoded column (DColumn pointers)
+  const uint8_t* row_def; const int64_t* row_offs; const uint8_t* entry_def;
+  const uint8_t* fixed; const int64_t* offs; const uint8_t* chars;
+  int32_t width, is_str, repeated, max_def;
+  int32_t null_only, pad;      // no value anywhere: only row_def is gathered
+  const int32_t* rows;
+  int64_t nr;                  // rows of the window
+  // per output row: entries (repeated) and chars, counted by k_exp_count, then scanned (exclusive)
+  // into the row's first output entry / char
+  long long* cnt_e; long long* cnt_c;
+  const long long* eb; const long long* cb;
+  int64_t nv, nc;              // output values (rows, or entries of a repeated leaf) and chars
+  // per output entry of a repeated leaf: its source entry and its output row (k_exp_rows)
+  int64_t* esrc; int32_t* erow;
+  // outputs (the window's layout, dk_batch_column)
+  uint8_t* o_rowdef; int32_t* o_rowoffs; uint8_t* o_entdef; unsigned long long* o_bits;
+  uint8_t* o_fixed; int32_t* o_offs; uint8_t* o_chars;
+};
+
 // deletion vectors: one roaring container of one DV (dk_dv.hip)
 enum : int32_t { DV_ARRAY = 0, DV_BITMAP = 1, DV_RUN = 2 };
 struct DvCont {

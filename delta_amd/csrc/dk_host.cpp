@@ -39,6 +39,13 @@ void launch_pack_bits(const uint8_t*, long long, uint8_t*, hipStream_t);
 void launch_expand(const int64_t*, const int32_t*, int, int, void*, hipStream_t);
 void launch_copy_zc(void*, const void*, long long, hipStream_t);
 void launch_arrow_window(const ArrowWin&, hipStream_t);
+void enc_exscan(const long long*, long long, long long*, long long*, long long*, hipStream_t);
+long long enc_scan_blocks(long long);
+long long exp_sel_waves(long long);
+void exp_sel_rows(const uint8_t*, long long, long long*, long long*, long long*, long long*, int32_t*, hipStream_t);
+void exp_count(const ExportLeaf&, hipStream_t);
+void exp_gather(const ExportLeaf&, hipStream_t);
+void exp_rowidx(const int32_t*, long long, int64_t*, hipStream_t);
 void launch_dv_expand(const DvCont*, int, const uint8_t*, unsigned long long*, hipStream_t);
 void launch_dv_select(const unsigned long long*, long long, const long long*, long long, uint8_t*, hipStream_t);
 void launch_positions(const DChunk*, DPage*, int, int, const uint8_t*, int32_t*, DPosChunk*, int, int, int16_t*, hipStream_t);
@@ -3963,6 +3970,10 @@ static int install_part(DevPart& d, const dk_program& src) {
   return 0;
 }
 
+struct dk_scan_reader;
+// a new run or the replay's end: open scan readers (dk_replay_scan_open) lose their replay
+static void replay_drop_scans(dk_replay* r);
+
 struct dk_replay {
   StreamH own;                          // the replay's stream (the checkpoint decode runs on it too)
   hipStream_t stream = nullptr;
@@ -4056,6 +4067,8 @@ struct dk_replay {
   std::vector<uint8_t> file_ready;        // dk_replay_wait_file passed for the file
   bool tail_ready = false;
   StreamH aux;                            // error-state reads while a grouped run is in flight
+  std::mutex scan_mu;
+  std::vector<dk_scan_reader*> scans;     // open scan readers over this replay's result
 };
 
 static const DColumn* find_col(dk_parquet* p, int fi, const char* leaf) {
@@ -4970,6 +4983,7 @@ static int replay_ckpt_filters(dk_replay* r) {
 static int owner_launch(dk_replay* r);
 extern "C" int dk_replay_run(dk_replay* r) {
   hipSetDevice(r->eng->cfg.device);
+  replay_drop_scans(r);
   r->have_result = false;
   r->h_csel_ready = false;
   if (r->ck && invalidate_mirrors(r->ck)) return 1;
@@ -4987,6 +5001,7 @@ extern "C" int dk_replay_run_grouped(dk_replay* r, int32_t n_groups) {
   if (n_groups < 1) return fail("dk_replay_run_grouped: n_groups must be >= 1");
   if (r->ow > 0) return fail("dk_replay_run_grouped: owner mode runs ungrouped (dk_replay_run)");
   hipSetDevice(r->eng->cfg.device);
+  replay_drop_scans(r);
   r->have_result = false;
   r->h_csel_ready = false;
   r->tail_ready = false;
@@ -5735,6 +5750,7 @@ extern "C" int dk_replay_kernel_stats(dk_replay* r, int32_t i, const char** name
 extern "C" void dk_replay_free(dk_replay* r) {
   if (!r) return;
   hipSetDevice(r->eng->cfg.device);
+  replay_drop_scans(r);
   // the attached checkpoint set forgets this run's group events now (it may be closed next); the
   // rest -- events, blocks back to the caches, the streams -- is released in the background, like a
   // closed checkpoint set (close 3 -> 0.1 ms at C3)
@@ -5780,6 +5796,7 @@ struct PinnedBuf {
 
 struct WinLeaf {                 // one leaf's buffers inside a window (offsets into the host buffer)
   int present = 0, null_only = 0;
+  int phys = 0, width = 0, max_def = 0, max_rep = 0, rep_def = 0;
   int64_t nv = 0, nchars = 0;
   size_t o_rowdef = 0, o_entdef = 0, o_fixed = 0, o_chars = 0, o_bits = 0, o_offs = 0, o_rowoffs = 0;
 };
@@ -5790,13 +5807,30 @@ struct RWin {                    // rows [r0, r0 + nr) of one file in pinned hos
   PinnedBuf buf;
   std::vector<WinLeaf> leaf;
   size_t o_rowidx = 0;
+  size_t o_sel = 0;              // scan reader, compact = 0: one selection byte per row
+  bool has_rowidx = false, has_sel = false;
   int refs = 0;                  // outstanding batches (+1 while it is the reader's current window)
+};
+
+// What the two batch readers (dk_reader, dk_scan_reader) share, and what a batch points back to: the
+// reader's stream, its windows and the count of live batches. A closed reader is freed with its last
+// batch (dk_batch_release, possibly on another thread).
+struct BatchOwner {
+  StreamH own;                   // first member: destroyed after every buffer of the reader
+  RWin* cur = nullptr;
+  std::vector<RWin*> pool;       // windows no batch refers to any more
+  std::mutex mu;                 // batches may be released from other threads
+  int outstanding = 0;           // live batches
+  bool closed = false;
+  virtual ~BatchOwner() {
+    delete cur;
+    for (RWin* w : pool) delete w;
+  }
 };
 
 }  // namespace
 
-struct dk_reader {
-  StreamH own;
+struct dk_reader : BatchOwner {
   dk_engine* eng = nullptr;
   dk_parquet* p = nullptr;
   std::vector<std::string> leaves;
@@ -5805,17 +5839,11 @@ struct dk_reader {
   bool row_index = false;
   int file = 0;
   int64_t next = 0;              // next row of `file`
-  RWin* cur = nullptr;
-  std::vector<RWin*> pool;       // windows no batch refers to any more
-  std::mutex mu;                 // batches may be released from other threads
-  int outstanding = 0;           // live batches
-  bool closed = false;
   DBuf d_stage, d_ovf;
+  HBuf h_rng;
   // row-index map per file: (first selected row, file row) of every selected row group
   std::vector<std::vector<std::pair<int64_t, int64_t>>> rgmap;
-  ~dk_reader() {
-    delete cur;
-    for (RWin* w : pool) delete w;
+  ~dk_reader() override {
     if (p) dk_parquet_close(p);
   }
 };
@@ -5823,11 +5851,11 @@ struct dk_reader {
 struct dk_batch_impl {
   dk_batch pub;
   std::vector<dk_batch_column> cols;
-  dk_reader* rd;
+  BatchOwner* rd;
   RWin* win;
 };
 
-static void reader_maybe_free(dk_reader* r, std::unique_lock<std::mutex>& lk) {
+static void reader_maybe_free(BatchOwner* r, std::unique_lock<std::mutex>& lk) {
   if (r->closed && r->outstanding == 0) { lk.unlock(); delete r; }
 }
 
@@ -5869,38 +5897,79 @@ extern "C" int dk_reader_open(dk_engine* e, const char* const* paths, int32_t n_
   return 0;
 }
 
-// file rows [r0, r0 + nr) of the reader's current file into a window
-static int load_window(dk_reader* r, RWin* w, int64_t r0, int64_t nr) {
-  dk_parquet* p = r->p;
-  const int fi = r->file;
-  const hipStream_t s = r->own.s;
-  const size_t nl = r->leaves.size();
+// What load_window reads from: one file of a decoded set on the reader's stream. The streaming reader
+// projects exactly the set's leaves; the scan reader a subset (pleaf) plus the replay's selection.
+struct WinCtx {
+  dk_parquet* p = nullptr;
+  int fi = 0;
+  hipStream_t s = nullptr;
+  int B = 1024;
+  size_t nl = 0;
+  const std::vector<int>* pleaf = nullptr;   // reader leaf -> leaf of p (null: the same leaves)
+  bool row_index = false;
+  const std::vector<std::pair<int64_t, int64_t>>* rgmap = nullptr;
+  bool want_sel = false;
+  const uint8_t* d_sel = nullptr;            // the file's selection bytes in HBM (null: none selected)
+  DBuf* d_stage = nullptr;
+  DBuf* d_ovf = nullptr;
+  HBuf* h_rng = nullptr;                     // pinned: the windows' value / char ranges
+  int64_t* d2h = nullptr;                    // += the window's device-to-host bytes
+  int col(size_t li) const {
+    const int pl = pleaf ? (*pleaf)[li] : (int)li;
+    return pl < 0 ? -1 : p->colmap[fi][pl];
+  }
+};
+
+// file rows [r0, r0 + nr) of one file into a window
+static int load_window(const WinCtx& X, RWin* w, int64_t r0, int64_t nr) {
+  dk_parquet* p = X.p;
+  const int fi = X.fi;
+  const hipStream_t s = X.s;
+  const size_t nl = X.nl;
   w->file = fi; w->r0 = r0; w->leaf.assign(nl, WinLeaf());
-  // value / char ranges of the window (two int64 per leaf and level from HBM)
+  // value / char ranges of the window (two int64 per leaf and level from HBM, stream-ordered copies
+  // into pinned memory: one round for the entry ranges, one for the char ranges)
   struct Rng { int64_t v0 = 0, v1 = 0, c0 = 0, c1 = 0; };
   std::vector<Rng> rg(nl);
+  if (X.h_rng->size() < nl * 32 + 64 && X.h_rng->alloc(nl * 32 + 64)) return 1;
+  int64_t* hr = (int64_t*)X.h_rng->data();
   for (;;) {
     bool fits = true;
     for (size_t li = 0; li < nl; li++) {
-      const int ci = p->colmap[fi][li];
+      const int ci = X.col(li);
+      if (ci < 0) continue;
+      const DColumn& c = p->h_cols[ci];
+      if (c.null_only || c.max_rep == 0) continue;
+      HIPOK(hipMemcpyAsync(hr + 4 * li, c.row_offs + r0, 8, hipMemcpyDeviceToHost, s));
+      HIPOK(hipMemcpyAsync(hr + 4 * li + 1, c.row_offs + r0 + nr, 8, hipMemcpyDeviceToHost, s));
+    }
+    HIPOK(hipStreamSynchronize(s));
+    for (size_t li = 0; li < nl; li++) {
+      const int ci = X.col(li);
       if (ci < 0) continue;
       const DColumn& c = p->h_cols[ci];
       Rng& q = rg[li];
       q = Rng();
       if (c.null_only) { q.v0 = c.max_rep > 0 ? 0 : r0; q.v1 = c.max_rep > 0 ? 0 : r0 + nr; continue; }
-      if (c.max_rep > 0) {
-        HIPOK(hipMemcpy(&q.v0, c.row_offs + r0, 8, hipMemcpyDeviceToHost));
-        HIPOK(hipMemcpy(&q.v1, c.row_offs + r0 + nr, 8, hipMemcpyDeviceToHost));
-      } else { q.v0 = r0; q.v1 = r0 + nr; }
+      if (c.max_rep > 0) { q.v0 = hr[4 * li]; q.v1 = hr[4 * li + 1]; }
+      else { q.v0 = r0; q.v1 = r0 + nr; }
       if (c.phys == PT_BYTE_ARRAY) {
-        HIPOK(hipMemcpy(&q.c0, c.offs + q.v0, 8, hipMemcpyDeviceToHost));
-        HIPOK(hipMemcpy(&q.c1, c.offs + q.v1, 8, hipMemcpyDeviceToHost));
+        HIPOK(hipMemcpyAsync(hr + 4 * li + 2, c.offs + q.v0, 8, hipMemcpyDeviceToHost, s));
+        HIPOK(hipMemcpyAsync(hr + 4 * li + 3, c.offs + q.v1, 8, hipMemcpyDeviceToHost, s));
       }
+    }
+    HIPOK(hipStreamSynchronize(s));
+    for (size_t li = 0; li < nl; li++) {
+      const int ci = X.col(li);
+      if (ci < 0) continue;
+      const DColumn& c = p->h_cols[ci];
+      Rng& q = rg[li];
+      if (!c.null_only && c.phys == PT_BYTE_ARRAY) { q.c0 = hr[4 * li + 2]; q.c1 = hr[4 * li + 3]; }
       if (q.c1 - q.c0 >= (1ll << 31) - 1 || q.v1 - q.v0 >= (1ll << 31) - 1) fits = false;
     }
     if (fits) break;
-    if (nr <= r->B) return fail("Error reading Parquet file: " + p->files[fi].path + " (a batch exceeds 2 GiB)");
-    nr = std::max<int64_t>(r->B, nr / 2 / r->B * r->B);           // int32 offsets: a smaller window
+    if (nr <= X.B) return fail("Error reading Parquet file: " + p->files[fi].path + " (a batch exceeds 2 GiB)");
+    nr = std::max<int64_t>(X.B, nr / 2 / X.B * X.B);           // int32 offsets: a smaller window
   }
   w->nr = nr;
   // host layout, 64-byte aligned pieces; device staging for bits + int32 offsets
@@ -5908,12 +5977,13 @@ static int load_window(dk_reader* r, RWin* w, int64_t r0, int64_t nr) {
   auto take = [](size_t& at, size_t n) { at = (at + 63) & ~(size_t)63; const size_t o = at; at += n; return o; };
   std::vector<size_t> d_bits(nl), d_offs(nl), d_roffs(nl);
   for (size_t li = 0; li < nl; li++) {
-    const int ci = p->colmap[fi][li];
+    const int ci = X.col(li);
     WinLeaf& L = w->leaf[li];
     L.o_rowdef = take(hsz, nr);
     if (ci < 0) continue;
     const DColumn& c = p->h_cols[ci];
     L.present = 1; L.null_only = c.null_only;
+    L.phys = c.phys; L.width = c.width; L.max_def = c.max_def; L.max_rep = c.max_rep; L.rep_def = c.rep_def;
     L.nv = rg[li].v1 - rg[li].v0;
     L.nchars = rg[li].c1 - rg[li].c0;
     if (c.max_rep > 0) { L.o_entdef = take(hsz, L.nv); L.o_rowoffs = take(hsz, 4 * (nr + 1)); d_roffs[li] = take(dsz, 4 * (nr + 1)); }
@@ -5925,14 +5995,20 @@ static int load_window(dk_reader* r, RWin* w, int64_t r0, int64_t nr) {
       L.o_fixed = take(hsz, (size_t)L.nv * c.width);
     }
   }
-  if (r->row_index) w->o_rowidx = take(hsz, 8 * nr);
+  w->has_rowidx = X.row_index; w->has_sel = X.want_sel;
+  if (X.row_index) w->o_rowidx = take(hsz, 8 * nr);
+  if (X.want_sel) w->o_sel = take(hsz, nr);
   if (w->buf.reserve(hsz + 64)) return 1;
-  if (dsz > r->d_stage.n && r->d_stage.alloc(dsz + 64)) return 1;
+  if (dsz > X.d_stage->n && X.d_stage->alloc(dsz + 64)) return 1;
   uint8_t* H = w->buf.p;
-  uint8_t* D = r->d_stage.as<uint8_t>();
-  HIPOK(hipMemsetAsync(r->d_ovf.p, 0, 4, s));
+  uint8_t* D = X.d_stage->as<uint8_t>();
+  HIPOK(hipMemsetAsync(X.d_ovf->p, 0, 4, s));
+  if (X.want_sel) {
+    if (X.d_sel) HIPOK(hipMemcpyAsync(H + w->o_sel, X.d_sel + r0, nr, hipMemcpyDeviceToHost, s));
+    else memset(H + w->o_sel, 0, nr);
+  }
   for (size_t li = 0; li < nl; li++) {
-    const int ci = p->colmap[fi][li];
+    const int ci = X.col(li);
     WinLeaf& L = w->leaf[li];
     if (ci < 0) { memset(H + L.o_rowdef, 0, nr); continue; }
     const DColumn& c = p->h_cols[ci];
@@ -5953,7 +6029,7 @@ static int load_window(dk_reader* r, RWin* w, int64_t r0, int64_t nr) {
     A.bits = (uint64_t*)(D + d_bits[li]);
     A.offs32 = (int32_t*)(D + d_offs[li]);
     A.row_offs32 = (int32_t*)(D + d_roffs[li]);
-    A.overflow = r->d_ovf.as<int32_t>();
+    A.overflow = X.d_ovf->as<int32_t>();
     launch_arrow_window(A, s);
     HIPOK(hipMemcpyAsync(H + L.o_bits, D + d_bits[li], 8 * ((L.nv + 63) / 64), hipMemcpyDeviceToHost, s));
     if (c.max_rep > 0) {
@@ -5969,9 +6045,10 @@ static int load_window(dk_reader* r, RWin* w, int64_t r0, int64_t nr) {
   }
   // row index: the file row of each selected row (row groups pruned by the predicate are skipped,
   // as parquet-mr's getCurrentRowIndex counts them)
-  if (r->row_index) {
+  if (X.row_index) {
     int64_t* ri = (int64_t*)(H + w->o_rowidx);
-    const auto& m = r->rgmap[fi];
+    static const std::vector<std::pair<int64_t, int64_t>> none;
+    const auto& m = X.rgmap ? *X.rgmap : none;
     size_t k = 0;
     for (int64_t i = 0; i < nr; i++) {
       const int64_t row = r0 + i;
@@ -5979,13 +6056,28 @@ static int load_window(dk_reader* r, RWin* w, int64_t r0, int64_t nr) {
       ri[i] = m.empty() ? row : m[k].second + (row - m[k].first);
     }
   }
-  int32_t ovf = 0;
-  HIPOK(hipMemcpyAsync(&ovf, r->d_ovf.p, 4, hipMemcpyDeviceToHost, s));
+  if (X.d2h) {
+    int64_t moved = X.want_sel && X.d_sel ? nr : 0;
+    for (size_t li = 0; li < nl; li++) {
+      const WinLeaf& L = w->leaf[li];
+      if (!L.present) continue;
+      moved += nr;
+      if (L.null_only) continue;
+      moved += 8 * ((L.nv + 63) / 64);
+      if (L.max_rep > 0) moved += 4 * (nr + 1) + L.nv;
+      moved += L.phys == PT_BYTE_ARRAY ? 4 * (L.nv + 1) + L.nchars : L.nv * L.width;
+    }
+    *X.d2h += moved;
+  }
+  int32_t* ovf_h = (int32_t*)(hr + 4 * nl);
+  HIPOK(hipMemcpyAsync(ovf_h, X.d_ovf->p, 4, hipMemcpyDeviceToHost, s));
   HIPOK(hipStreamSynchronize(s));
+  const int32_t ovf = *ovf_h;
   if (ovf) return fail("Error reading Parquet file: " + p->files[fi].path + " (int32 offset overflow)");
   return 0;
 }
 
+static dk_batch_impl* make_batch(BatchOwner* o, RWin* w, int64_t rb, int64_t nb);
 extern "C" int dk_reader_next(dk_reader* r, dk_batch** out) {
   *out = nullptr;
   if (!r) return fail("null reader");
@@ -6003,7 +6095,11 @@ extern "C" int dk_reader_next(dk_reader* r, dk_batch** out) {
         if (!r->pool.empty()) { w = r->pool.back(); r->pool.pop_back(); }
       }
       if (!w) w = new RWin();
-      if (load_window(r, w, r->next, std::min<int64_t>(r->W, n - r->next))) {
+      WinCtx X;
+      X.p = p; X.fi = r->file; X.s = r->own.s; X.B = r->B; X.nl = r->leaves.size();
+      X.row_index = r->row_index; X.rgmap = &r->rgmap[r->file];
+      X.d_stage = &r->d_stage; X.d_ovf = &r->d_ovf; X.h_rng = &r->h_rng;
+      if (load_window(X, w, r->next, std::min<int64_t>(r->W, n - r->next))) {
         std::lock_guard<std::mutex> g(r->mu);
         r->pool.push_back(w);
         return 1;
@@ -6016,17 +6112,25 @@ extern "C" int dk_reader_next(dk_reader* r, dk_batch** out) {
   RWin* w = r->cur;
   const int64_t b0 = r->next, b1 = std::min<int64_t>(b0 + r->B, w->r0 + w->nr);
   const int64_t rb = b0 - w->r0, nb = b1 - b0;
+  dk_batch_impl* b = make_batch(r, w, rb, nb);
+  r->next = b1;
+  *out = &b->pub;
+  return 0;
+}
+
+// rows [rb, rb + nb) of a loaded window as a batch of `o` (dk_batch_column's layout)
+static dk_batch_impl* make_batch(BatchOwner* o, RWin* w, int64_t rb, int64_t nb) {
   auto* b = new dk_batch_impl();
-  b->rd = r; b->win = w;
-  b->cols.resize(r->leaves.size());
+  b->rd = o; b->win = w;
+  b->cols.resize(w->leaf.size());
   uint8_t* H = w->buf.p;
-  for (size_t li = 0; li < r->leaves.size(); li++) {
+  for (size_t li = 0; li < w->leaf.size(); li++) {
     const WinLeaf& L = w->leaf[li];
     dk_batch_column& c = b->cols[li];
     memset(&c, 0, sizeof c);
     c.row_def = H + L.o_rowdef + rb;
     if (!L.present) { c.present = 0; c.n_values = nb; continue; }
-    const DColumn& d = p->h_cols[p->colmap[w->file][li]];
+    const WinLeaf& d = L;
     c.present = 1; c.phys = d.phys; c.width = d.width; c.max_def = d.max_def; c.max_rep = d.max_rep; c.rep_def = d.rep_def;
     c.validity = H + L.o_bits;
     if (d.max_rep > 0) {
@@ -6045,21 +6149,19 @@ extern "C" int dk_reader_next(dk_reader* r, dk_batch** out) {
   b->pub.n_rows = nb;
   b->pub.n_cols = (int32_t)b->cols.size();
   b->pub.cols = b->cols.data();
-  b->pub.row_index = r->row_index ? (const int64_t*)(H + w->o_rowidx) + rb : nullptr;
+  b->pub.row_index = w->has_rowidx ? (const int64_t*)(H + w->o_rowidx) + rb : nullptr;
   {
-    std::lock_guard<std::mutex> g(r->mu);
+    std::lock_guard<std::mutex> g(o->mu);
     w->refs++;
-    r->outstanding++;
+    o->outstanding++;
   }
-  r->next = b1;
-  *out = &b->pub;
-  return 0;
+  return b;
 }
 
 extern "C" void dk_batch_release(dk_batch* pub) {
   if (!pub) return;
   dk_batch_impl* b = reinterpret_cast<dk_batch_impl*>(pub);   // pub is the first member
-  dk_reader* r = b->rd;
+  BatchOwner* r = b->rd;
   std::unique_lock<std::mutex> lk(r->mu);
   if (--b->win->refs == 0) r->pool.push_back(b->win);
   r->outstanding--;
@@ -6079,6 +6181,425 @@ extern "C" void dk_reader_close(dk_reader* r) {
 
 extern "C" int64_t dk_reader_num_rows(dk_reader* r, int32_t file) {
   return r ? dk_parquet_num_rows(r->p, file) : -1;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Scan-file batch reader (dk_replay_scan_open / dk_scan_next / dk_scan_close): Scan.getScanFiles'
+// CloseableIterator<FilteredColumnarBatch> over a finished replay, in dk_batch's Arrow-style layout
+// (DESIGN.md "Scan-file batch reader"). Sources in Appendix B order: the commit tail's rows, a V2 JSON
+// manifest's rows, then the checkpoint files in replay order. compact = 1 emits only the selected
+// rows: per checkpoint file an ordered list of selected rows is built once on the device, windows are
+// ranges of that list, and each leaf's rows are gathered from the decoded column into device staging
+// laid out as the host window (dk_export.hip), which crosses PCIe in one stream-ordered copy.
+// compact = 0 is load_window over the replay's checkpoint plus the selection slice. The tail's rows
+// are already host memory (dk_json_tail); their windows are converted on the host. All device work
+// runs on the reader's own stream, ordered after the replay's stream by an event.
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct ScanSrc { int file; int64_t a, b; };   // file >= 0: checkpoint file; -1 tail / -2 manifest: tail rows [a, b)
+int grow(DBuf& d, size_t n) { return d.n >= n && d.p ? 0 : d.alloc(n); }
+int grow(HBuf& h, size_t n) { return h.size() >= n && h.data() ? 0 : h.alloc(n); }
+}  // namespace
+
+struct dk_scan_reader : BatchOwner {
+  dk_engine* eng = nullptr;
+  dk_replay* rp = nullptr;           // null once the replay ran again or was freed
+  std::vector<std::string> leaves;
+  std::vector<int> pleaf;            // leaf of the checkpoint set (-1: none)
+  std::vector<int> jleaf;            // commit-tail leaf (JSON_LEAVES index, -1: none)
+  bool compact = true;
+  int B = 1024;
+  int64_t W = 1 << 20;
+  hipEvent_t ev = nullptr;
+  std::vector<ScanSrc> src;
+  size_t si = 0;                     // current source
+  int64_t next = 0;                  // next emitted row of the source (compact: index into its row list)
+  int64_t src_n = -1;                // rows the source emits (-1: not prepared yet)
+  std::vector<uint8_t> tsel;         // the tail's selection, one byte per tail row
+  std::vector<int64_t> trows;        // tail source: the tail rows it emits
+  DBuf d_rows, d_wcnt, d_wbase, d_sums, d_total, d_stage, d_ovf, d_cnt, d_ent;
+  HBuf h_rng, h_tot;
+  int64_t stats[4] = {0, 0, 0, 0};   // D2H bytes, windows, rows, batches
+  ~dk_scan_reader() override { if (ev) hipEventDestroy(ev); }
+};
+
+static void replay_drop_scans(dk_replay* r) {
+  std::lock_guard<std::mutex> g(r->scan_mu);
+  for (dk_scan_reader* s : r->scans) s->rp = nullptr;
+  r->scans.clear();
+}
+
+extern "C" int dk_replay_scan_open(dk_replay* r, const char* const* leaves, int32_t n_leaves, const dk_scan_options* opt,
+                                   dk_scan_reader** out) {
+  if (!out) return fail("dk_replay_scan_open: null out");
+  *out = nullptr;
+  if (!r) return fail("dk_replay_scan_open: null replay");
+  if (r->ow > 0 || r->xw > 0)
+    return fail("dk_replay_scan_open: owner and exchange (multi-GPU) replays are not supported");
+  if (!r->have_result) return fail("dk_replay_scan_open: the replay has no result (dk_replay_run, then dk_replay_sync)");
+  if (n_leaves < 0 || (n_leaves > 0 && !leaves)) return fail("dk_replay_scan_open: bad leaves");
+  hipSetDevice(r->eng->cfg.device);
+  std::unique_ptr<dk_scan_reader> s(new dk_scan_reader());
+  s->eng = r->eng; s->rp = r;
+  s->compact = !opt || opt->compact != 0;
+  s->B = opt && opt->batch_rows > 0 ? opt->batch_rows : (r->eng->cfg.parquet_batch_size > 0 ? r->eng->cfg.parquet_batch_size : 1024);
+  if (opt && opt->window_rows > 0) s->W = opt->window_rows;
+  s->W = std::max<int64_t>(s->B, s->W / s->B * s->B);
+  for (int i = 0; i < n_leaves; i++) {
+    if (!leaves[i]) return fail("dk_replay_scan_open: null leaf");
+    int pl = -1, jl = -1;
+    if (r->ck) for (size_t k = 0; k < r->ck->leaves.size(); k++) if (r->ck->leaves[k] == leaves[i]) pl = (int)k;
+    for (int k = 0; k < JL_N; k++) if (!strcmp(JSON_LEAVES[k], leaves[i])) jl = k;
+    if (r->ck ? pl < 0 : jl < 0) return fail(std::string("dk_replay_scan_open: leaf not projected: ") + leaves[i]);
+    if (jl == JL_STATS && r->tail && !r->tail->with_stats) jl = -1;
+    if (jl >= JL_RPATH) jl = -1;               // scan files are add rows
+    s->leaves.push_back(leaves[i]); s->pleaf.push_back(pl); s->jleaf.push_back(jl);
+  }
+  if (s->own.create()) return 1;
+  if (hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) return fail("hipEventCreate failed");
+  const hipStream_t st = s->own.s;
+  HIPOK(hipEventRecord(s->ev, r->stream));
+  HIPOK(hipStreamWaitEvent(st, s->ev, 0));
+  if (s->d_ovf.alloc(16) || s->d_total.alloc(64)) return 1;
+  if (r->ck && ensure_open(r->ck)) return 1;
+  // the commit tail's selection (one byte per action on the device -> one per tail row)
+  if (r->tail && r->tail->rows > 0) {
+    s->tsel.assign((size_t)r->tail->rows, 0);
+    const size_t na = r->acts.size();
+    if (na) {
+      if (grow(s->h_tot, na + 64)) return 1;
+      HIPOK(hipMemcpyAsync(s->h_tot.data(), r->d_jsel.p, na, hipMemcpyDeviceToHost, st));
+      HIPOK(hipStreamSynchronize(st));
+      const uint8_t* js = s->h_tot.data();
+      for (size_t i = 0; i < na; i++) if (r->acts[i].kind != JA_REMOVE && js[i]) s->tsel[(size_t)r->act_row[i]] = 1;
+    }
+    const int64_t r0 = r->tail->ckpt_row0 >= 0 ? r->tail->ckpt_row0 : r->tail->rows;
+    if (r0 > 0) s->src.push_back({-1, 0, r0});
+    if (r0 < r->tail->rows) s->src.push_back({-2, r0, r->tail->rows});
+  }
+  if (r->ck) for (int f = 0; f < (int)r->ck->files.size(); f++) s->src.push_back({f, 0, r->ck->files[f].num_rows});
+  {
+    std::lock_guard<std::mutex> g(r->scan_mu);
+    r->scans.push_back(s.get());
+  }
+  *out = s.release();
+  return 0;
+}
+
+// the rows a source emits: all of them, or (compact) the selected ones -- for a checkpoint file the
+// ordered list of its selected rows, built on the device
+static int scan_prepare_source(dk_scan_reader* s) {
+  dk_replay* r = s->rp;
+  const ScanSrc& S = s->src[s->si];
+  const hipStream_t st = s->own.s;
+  if (S.file < 0) {
+    s->trows.clear();
+    for (int64_t i = S.a; i < S.b; i++) if (!s->compact || s->tsel[(size_t)i]) s->trows.push_back(i);
+    s->src_n = (int64_t)s->trows.size();
+    return 0;
+  }
+  const int64_t n = S.b;
+  if (!s->compact) { s->src_n = n; return 0; }
+  if (n == 0 || r->probe[S.file].n_rows == 0) { s->src_n = 0; return 0; }   // (no add.path: nothing selected)
+  if (n >= (1ll << 31) - 1) return fail("dk_scan_next: a checkpoint file of 2^31 rows or more");
+  const long long nw = exp_sel_waves(n);
+  if (grow(s->d_rows, (size_t)n * 4 + 64) || grow(s->d_wcnt, (size_t)nw * 8 + 64) || grow(s->d_wbase, (size_t)nw * 8 + 64) ||
+      grow(s->d_sums, (size_t)enc_scan_blocks(nw) * 8 + 64) || grow(s->h_tot, 64)) return 1;
+  exp_sel_rows(r->d_csel[S.file]->as<uint8_t>(), n, s->d_wcnt.as<long long>(), s->d_wbase.as<long long>(),
+               s->d_sums.as<long long>(), s->d_total.as<long long>(), s->d_rows.as<int32_t>(), st);
+  HIPOK(hipMemcpyAsync(s->h_tot.data(), s->d_total.p, 8, hipMemcpyDeviceToHost, st));
+  HIPOK(hipStreamSynchronize(st));
+  s->src_n = *(const long long*)s->h_tot.data();
+  if (s->src_n < 0 || s->src_n > n) return fail("dk_scan_next: internal error: bad selected-row count");
+  return 0;
+}
+
+static size_t win_take(size_t& at, size_t n) { at = (at + 63) & ~(size_t)63; const size_t o = at; at += n; return o; }
+
+// compact mode, checkpoint file: rows [j0, j0 + nr) of the file's selected-row list into a window
+static int gather_window(dk_scan_reader* s, RWin* w, int fi, int64_t j0, int64_t nr) {
+  dk_replay* r = s->rp;
+  dk_parquet* p = r->ck;
+  const hipStream_t st = s->own.s;
+  const size_t nl = s->leaves.size();
+  w->file = fi; w->r0 = j0; w->leaf.assign(nl, WinLeaf());
+  std::vector<ExportLeaf> E(nl);
+  std::vector<int> ci(nl, -1);
+  size_t n_cnt = 0;                        // leaves whose entries / chars are counted
+  for (size_t li = 0; li < nl; li++) {
+    ci[li] = s->pleaf[li] < 0 ? -1 : p->colmap[fi][s->pleaf[li]];
+    if (ci[li] < 0) continue;
+    const DColumn& c = p->h_cols[ci[li]];
+    if (!c.null_only && (c.max_rep > 0 || c.phys == PT_BYTE_ARRAY)) n_cnt++;
+  }
+  if (grow(s->h_tot, nl * 16 + 64)) return 1;
+  long long* tot = (long long*)s->h_tot.data();
+  for (;;) {
+    const int32_t* rows = s->d_rows.as<int32_t>() + j0;
+    if (grow(s->d_cnt, n_cnt * 4 * (size_t)(nr + 1) * 8 + 64) || grow(s->d_sums, (size_t)enc_scan_blocks(nr + 1) * 8 + 64)) return 1;
+    long long* cnt = s->d_cnt.as<long long>();
+    size_t k = 0;
+    for (size_t li = 0; li < nl; li++) {
+      ExportLeaf& L = E[li];
+      L = ExportLeaf();
+      tot[2 * li] = tot[2 * li + 1] = 0;
+      if (ci[li] < 0) continue;
+      const DColumn& c = p->h_cols[ci[li]];
+      L.row_def = c.row_def; L.row_offs = c.row_offs; L.entry_def = c.entry_def;
+      L.fixed = c.fixed; L.offs = c.offs; L.chars = c.chars;
+      L.width = c.width; L.is_str = c.phys == PT_BYTE_ARRAY; L.repeated = c.max_rep > 0; L.max_def = c.max_def;
+      L.null_only = c.null_only;
+      L.rows = rows; L.nr = nr;
+      if (c.null_only || (!L.repeated && !L.is_str)) continue;
+      long long* base = cnt + k++ * 4 * (size_t)(nr + 1);
+      L.cnt_e = base; L.cnt_c = base + (nr + 1);
+      long long* eb = base + 2 * (nr + 1);
+      long long* cb = base + 3 * (nr + 1);
+      L.eb = eb; L.cb = cb;
+      exp_count(L, st);
+      if (L.repeated) {
+        enc_exscan(L.cnt_e, nr, eb, s->d_sums.as<long long>(), s->d_total.as<long long>(), st);
+        HIPOK(hipMemcpyAsync(&tot[2 * li], s->d_total.p, 8, hipMemcpyDeviceToHost, st));
+      }
+      if (L.is_str) {
+        enc_exscan(L.cnt_c, nr, cb, s->d_sums.as<long long>(), s->d_total.as<long long>(), st);
+        HIPOK(hipMemcpyAsync(&tot[2 * li + 1], s->d_total.p, 8, hipMemcpyDeviceToHost, st));
+      }
+    }
+    HIPOK(hipStreamSynchronize(st));
+    bool fits = true;
+    for (size_t li = 0; li < nl; li++)
+      if (tot[2 * li] >= (1ll << 31) - 1 || tot[2 * li + 1] >= (1ll << 31) - 1) fits = false;
+    if (fits) break;
+    if (nr <= s->B) return fail("Error reading scan files: " + p->files[fi].path + " (a batch exceeds 2 GiB)");
+    nr = std::max<int64_t>(s->B, nr / 2 / s->B * s->B);           // int32 offsets: a smaller window
+  }
+  w->nr = nr;
+  // layout: the pieces the device writes first (one copy), then the pieces the host zeroes
+  size_t hsz = 0, esz = 0;
+  for (size_t li = 0; li < nl; li++) {
+    WinLeaf& L = w->leaf[li];
+    if (ci[li] < 0) continue;
+    const DColumn& c = p->h_cols[ci[li]];
+    ExportLeaf& X = E[li];
+    L.present = 1; L.null_only = c.null_only;
+    L.phys = c.phys; L.width = c.width; L.max_def = c.max_def; L.max_rep = c.max_rep; L.rep_def = c.rep_def;
+    L.o_rowdef = win_take(hsz, nr);
+    if (c.null_only) { L.nv = c.max_rep > 0 ? 0 : nr; continue; }
+    L.nv = c.max_rep > 0 ? tot[2 * li] : nr;
+    L.nchars = tot[2 * li + 1];
+    X.nv = L.nv; X.nc = L.nchars;
+    if (c.max_rep > 0) {
+      L.o_entdef = win_take(hsz, L.nv); L.o_rowoffs = win_take(hsz, 4 * (nr + 1));
+      win_take(esz, 8 * (size_t)L.nv); win_take(esz, 4 * (size_t)L.nv);
+    }
+    L.o_bits = win_take(hsz, 8 * ((L.nv + 63) / 64));
+    if (c.phys == PT_BYTE_ARRAY) { L.o_offs = win_take(hsz, 4 * (L.nv + 1)); L.o_chars = win_take(hsz, L.nchars); }
+    else L.o_fixed = win_take(hsz, (size_t)L.nv * c.width);
+  }
+  w->has_rowidx = true; w->has_sel = false;
+  w->o_rowidx = win_take(hsz, 8 * nr);
+  const size_t dsz = hsz;
+  for (size_t li = 0; li < nl; li++) {
+    WinLeaf& L = w->leaf[li];
+    if (ci[li] < 0) { L.o_rowdef = win_take(hsz, nr); continue; }
+    if (!L.null_only) continue;
+    if (L.max_rep > 0) L.o_rowoffs = win_take(hsz, 4 * (nr + 1));
+    L.o_bits = win_take(hsz, 8 * ((L.nv + 63) / 64));
+    if (L.phys == PT_BYTE_ARRAY) L.o_offs = win_take(hsz, 4 * (L.nv + 1));
+    else L.o_fixed = win_take(hsz, (size_t)L.nv * L.width);
+  }
+  if (w->buf.reserve(hsz + 64) || grow(s->d_stage, dsz + 64) || grow(s->d_ent, esz + 64)) return 1;
+  uint8_t* H = w->buf.p;
+  uint8_t* D = s->d_stage.as<uint8_t>();
+  uint8_t* T = s->d_ent.as<uint8_t>();
+  size_t eat = 0;
+  for (size_t li = 0; li < nl; li++) {
+    const WinLeaf& L = w->leaf[li];
+    if (ci[li] < 0) continue;
+    ExportLeaf& X = E[li];
+    X.o_rowdef = D + L.o_rowdef;
+    if (!L.null_only) {
+      X.o_rowoffs = (int32_t*)(D + L.o_rowoffs); X.o_entdef = D + L.o_entdef;
+      X.o_bits = (unsigned long long*)(D + L.o_bits);
+      X.o_fixed = D + L.o_fixed; X.o_offs = (int32_t*)(D + L.o_offs); X.o_chars = D + L.o_chars;
+      if (L.max_rep > 0) { X.esrc = (int64_t*)(T + win_take(eat, 8 * (size_t)L.nv)); X.erow = (int32_t*)(T + win_take(eat, 4 * (size_t)L.nv)); }
+    }
+    exp_gather(X, st);
+  }
+  exp_rowidx(s->d_rows.as<int32_t>() + j0, nr, (int64_t*)(D + w->o_rowidx), st);
+  HIPOK(hipMemcpyAsync(H, D, dsz, hipMemcpyDeviceToHost, st));
+  if (hsz > dsz) memset(H + dsz, 0, hsz - dsz);      // absent and all-null leaves: no device work
+  HIPOK(hipStreamSynchronize(st));
+  s->stats[0] += (int64_t)dsz;
+  return 0;
+}
+
+// tail rows trows[j0, j0 + nr) into a window, converted on the host from the tail's columns
+static int tail_window(dk_scan_reader* s, RWin* w, int64_t j0, int64_t nr) {
+  dk_json_tail* t = s->rp->tail;
+  const size_t nl = s->leaves.size();
+  w->file = (int)s->si; w->r0 = j0; w->leaf.assign(nl, WinLeaf());
+  std::vector<int64_t> nv(nl), nc(nl);
+  for (;;) {
+    bool fits = true;
+    for (size_t li = 0; li < nl; li++) {
+      nv[li] = nr; nc[li] = 0;
+      if (s->jleaf[li] < 0) continue;
+      const CB& c = t->col[s->jleaf[li]];
+      if (c.max_rep > 0) nv[li] = 0;
+      for (int64_t j = j0; j < j0 + nr; j++) {
+        const int64_t r = s->trows[(size_t)j];
+        if (c.max_rep > 0) {
+          nv[li] += c.row_offs[r + 1] - c.row_offs[r];
+          if (c.phys == PT_BYTE_ARRAY) nc[li] += c.offs[c.row_offs[r + 1]] - c.offs[c.row_offs[r]];
+        } else if (c.phys == PT_BYTE_ARRAY) nc[li] += c.offs[r + 1] - c.offs[r];
+      }
+      if (nv[li] >= (1ll << 31) - 1 || nc[li] >= (1ll << 31) - 1) fits = false;
+    }
+    if (fits) break;
+    if (nr <= s->B) return fail("Error reading scan files: the commit tail (a batch exceeds 2 GiB)");
+    nr = std::max<int64_t>(s->B, nr / 2 / s->B * s->B);
+  }
+  w->nr = nr;
+  size_t hsz = 0;
+  for (size_t li = 0; li < nl; li++) {
+    WinLeaf& L = w->leaf[li];
+    L.o_rowdef = win_take(hsz, nr);
+    if (s->jleaf[li] < 0) continue;
+    const CB& c = t->col[s->jleaf[li]];
+    L.present = 1;
+    L.phys = c.phys; L.width = c.width; L.max_def = c.max_def; L.max_rep = c.max_rep; L.rep_def = c.rep_def;
+    L.nv = nv[li]; L.nchars = nc[li];
+    if (c.max_rep > 0) { L.o_entdef = win_take(hsz, L.nv); L.o_rowoffs = win_take(hsz, 4 * (nr + 1)); }
+    L.o_bits = win_take(hsz, 8 * ((L.nv + 63) / 64));
+    if (c.phys == PT_BYTE_ARRAY) { L.o_offs = win_take(hsz, 4 * (L.nv + 1)); L.o_chars = win_take(hsz, L.nchars); }
+    else L.o_fixed = win_take(hsz, (size_t)L.nv * c.width);
+  }
+  w->has_rowidx = true; w->has_sel = !s->compact;
+  w->o_rowidx = win_take(hsz, 8 * nr);
+  if (w->has_sel) w->o_sel = win_take(hsz, nr);
+  if (w->buf.reserve(hsz + 64)) return 1;
+  uint8_t* H = w->buf.p;
+  memset(H, 0, hsz);
+  const int64_t a = s->src[s->si].a;
+  for (int64_t j = 0; j < nr; j++) {
+    const int64_t r = s->trows[(size_t)(j0 + j)];
+    ((int64_t*)(H + w->o_rowidx))[j] = r - a;
+    if (w->has_sel) H[w->o_sel + j] = s->tsel[(size_t)r];
+  }
+  for (size_t li = 0; li < nl; li++) {
+    if (s->jleaf[li] < 0) continue;
+    const WinLeaf& L = w->leaf[li];
+    const CB& c = t->col[s->jleaf[li]];
+    const bool str = c.phys == PT_BYTE_ARRAY;
+    uint8_t* bits = H + L.o_bits;
+    int32_t* offs = (int32_t*)(H + L.o_offs);
+    int32_t* roffs = (int32_t*)(H + L.o_rowoffs);
+    int64_t v = 0, ch = 0;
+    auto value = [&](int64_t src, int def) {
+      if (def == c.max_def) bits[v >> 3] |= (uint8_t)(1u << (v & 7));
+      if (str) {
+        const int64_t n = c.offs[src + 1] - c.offs[src];
+        offs[v] = (int32_t)ch;
+        if (n) memcpy(H + L.o_chars + ch, c.chars.data() + c.offs[src], (size_t)n);
+        ch += n;
+      } else if (c.width) {
+        memcpy(H + L.o_fixed + v * c.width, c.fixed.data() + src * c.width, (size_t)c.width);
+      }
+      v++;
+    };
+    for (int64_t j = 0; j < nr; j++) {
+      const int64_t r = s->trows[(size_t)(j0 + j)];
+      H[L.o_rowdef + j] = c.row_def[r];
+      if (c.max_rep > 0) {
+        roffs[j] = (int32_t)v;
+        for (int64_t e = c.row_offs[r]; e < c.row_offs[r + 1]; e++) { H[L.o_entdef + v] = c.entry_def[e]; value(e, c.entry_def[e]); }
+      } else value(r, c.row_def[r]);
+    }
+    if (c.max_rep > 0) roffs[nr] = (int32_t)v;
+    if (str) offs[v] = (int32_t)ch;
+  }
+  return 0;
+}
+
+extern "C" int dk_scan_next(dk_scan_reader* s, dk_batch** out, const uint8_t** selection) {
+  if (!out) return fail("dk_scan_next: null out");
+  *out = nullptr;
+  if (selection) *selection = nullptr;
+  if (!s) return fail("dk_scan_next: null reader");
+  if (s->closed) return fail("dk_scan_next: the reader is closed");
+  if (!s->rp) return fail("dk_scan_next: the replay ran again or was freed (close the reader before either)");
+  hipSetDevice(s->eng->cfg.device);
+  for (;;) {
+    if (s->si >= s->src.size()) return 0;
+    if (s->src_n < 0 && scan_prepare_source(s)) return 1;
+    if (s->next >= s->src_n) { s->si++; s->next = 0; s->src_n = -1; continue; }
+    if (!s->cur || s->cur->file != (int)s->si || s->next >= s->cur->r0 + s->cur->nr) {
+      RWin* w = nullptr;
+      {
+        std::lock_guard<std::mutex> g(s->mu);
+        if (s->cur) { if (--s->cur->refs == 0) s->pool.push_back(s->cur); s->cur = nullptr; }
+        if (!s->pool.empty()) { w = s->pool.back(); s->pool.pop_back(); }
+      }
+      if (!w) w = new RWin();
+      const ScanSrc& S = s->src[s->si];
+      const int64_t nr = std::min<int64_t>(s->W, s->src_n - s->next);
+      int rc;
+      if (S.file < 0) rc = tail_window(s, w, s->next, nr);
+      else if (s->compact) rc = gather_window(s, w, S.file, s->next, nr);
+      else {
+        WinCtx X;
+        X.p = s->rp->ck; X.fi = S.file; X.s = s->own.s; X.B = s->B; X.nl = s->leaves.size(); X.pleaf = &s->pleaf;
+        X.row_index = true; X.want_sel = true;
+        X.d_sel = s->rp->probe[S.file].n_rows == 0 ? nullptr : s->rp->d_csel[S.file]->as<uint8_t>();
+        X.d_stage = &s->d_stage; X.d_ovf = &s->d_ovf; X.h_rng = &s->h_rng; X.d2h = &s->stats[0];
+        rc = load_window(X, w, s->next, nr);
+      }
+      if (rc) {
+        std::lock_guard<std::mutex> g(s->mu);
+        s->pool.push_back(w);
+        return 1;
+      }
+      w->file = (int)s->si;              // windows are keyed by their source
+      w->refs = 1;
+      s->cur = w;
+      s->stats[1]++;
+    }
+    break;
+  }
+  RWin* w = s->cur;
+  const int64_t b0 = s->next, b1 = std::min<int64_t>(b0 + s->B, w->r0 + w->nr);
+  const int64_t rb = b0 - w->r0, nb = b1 - b0;
+  dk_batch_impl* b = make_batch(s, w, rb, nb);
+  b->pub.file = s->src[s->si].file;
+  if (selection && w->has_sel) *selection = w->buf.p + w->o_sel + rb;
+  s->next = b1;
+  s->stats[2] += nb; s->stats[3]++;
+  *out = &b->pub;
+  return 0;
+}
+
+extern "C" int dk_scan_stats(dk_scan_reader* s, int64_t out[4]) {
+  if (!s || !out) return fail("dk_scan_stats: null argument");
+  for (int i = 0; i < 4; i++) out[i] = s->stats[i];
+  return 0;
+}
+
+extern "C" void dk_scan_close(dk_scan_reader* s) {
+  if (!s) return;
+  hipSetDevice(s->eng->cfg.device);
+  if (s->rp) {
+    std::lock_guard<std::mutex> g(s->rp->scan_mu);
+    auto& v = s->rp->scans;
+    v.erase(std::remove(v.begin(), v.end(), s), v.end());
+    s->rp = nullptr;
+  }
+  std::unique_lock<std::mutex> lk(s->mu);
+  if (s->closed) return;
+  s->closed = true;
+  if (s->cur) { if (--s->cur->refs == 0) s->pool.push_back(s->cur); s->cur = nullptr; }
+  reader_maybe_free(s, lk);
 }
 
 // ------------------------------------------------------------------------------------------------

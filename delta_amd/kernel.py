@@ -25,7 +25,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import (MAX_LEAF_DEPTH, Column, DkError, check, dk_batch, dk_column, dk_config, dk_dv_descriptor,
-                   dk_read_options, dk_rg_filter, lib)
+                   dk_read_options, dk_rg_filter, dk_scan_options, lib)
 
 ADD_LEAVES = ["add.path", "add.partitionValues.key_value.key", "add.partitionValues.key_value.value",
               "add.size", "add.modificationTime", "add.dataChange",
@@ -1120,6 +1120,95 @@ class FilteredColumnarBatch:
         return np.nonzero(self.selection)[0]
 
 
+@dataclass
+class ScanFileBatch:
+    """One batch of GpuScan.getScanFileBatches: at most batch_rows scan-file rows of one source in
+    the ParquetHandler reader's layout (BatchColumn: validity bits, int32 offsets). selection: bool
+    per row, or None in compact mode (every row of the batch is selected); row_index: the source row
+    of each row (the row within the checkpoint file, the tail or the manifest's rows); file_index:
+    the replay-order checkpoint file index, -1 for the commit tail, -2 for a V2 JSON manifest."""
+    columns: dict
+    table_root: str
+    size: int
+    selection: np.ndarray | None
+    row_index: np.ndarray
+    file_index: int
+    source: str = ""
+
+    def selected_rows(self):
+        if self.selection is None:
+            return np.arange(self.size)
+        return np.nonzero(self.selection)[0]
+
+
+class ScanFileReader:
+    """dk_scan_reader over a scan's finished replay (dk_replay_scan_open): next_raw() hands out the
+    library's dk_batch (released with release()), iterating yields ScanFileBatch copies. close()
+    early is safe; batches stay valid after it."""
+
+    def __init__(self, scan, compact=True, batch_rows=None, window_rows=0, leaves=None):
+        self.scan = scan
+        self.leaves = list(leaves) if leaves is not None else ADD_LEAVES + ([STATS_LEAF] if scan.read_stats else [])
+        opt = dk_scan_options(1 if compact else 0, int(batch_rows or 0), int(window_rows or 0))
+        self._h = C.c_void_p()
+        check(lib().dk_replay_scan_open(scan._rh, _cstrs(self.leaves), len(self.leaves), C.byref(opt),
+                                        C.byref(self._h)))
+
+    def next_raw(self):
+        """(dk_batch pointer, selection address or None), or None at the end."""
+        out, sel = C.POINTER(dk_batch)(), C.c_void_p()
+        check(lib().dk_scan_next(self._h, C.byref(out), C.byref(sel)))
+        return (out, sel.value) if out else None
+
+    @staticmethod
+    def release(raw):
+        lib().dk_batch_release(raw)
+
+    def stats(self):
+        """bytes copied from the device, windows loaded, rows and batches emitted so far."""
+        st = (C.c_int64 * 4)()
+        check(lib().dk_scan_stats(self._h, st))
+        return dict(d2h_bytes=int(st[0]), windows=int(st[1]), rows=int(st[2]), batches=int(st[3]))
+
+    def batch(self, raw, sel):
+        b = raw.contents
+        n = int(b.n_rows)
+        scan = self.scan
+        if b.file >= 0:
+            source = scan.ckpt_files[b.file]
+            fidx = scan.ckpt_index[b.file]
+        else:
+            source = "json-tail" if b.file == -1 else scan.snapshot._json_checkpoint_parts()[0]
+            fidx = int(b.file)
+        return ScanFileBatch({leaf: BatchColumn(b.cols[i], n, leaf) for i, leaf in enumerate(self.leaves)},
+                             scan.table_root(), n,
+                             _np_view(sel, n, np.uint8).astype(bool) if sel else None,
+                             _np_view(b.row_index, n, np.int64).copy(), fidx, source)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        got = self.next_raw()
+        if got is None:
+            raise StopIteration
+        try:
+            return self.batch(*got)
+        finally:
+            lib().dk_batch_release(got[0])
+
+    def close(self):
+        if self._h:
+            lib().dk_scan_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class GpuScan:
     """Scan whose getScanFiles runs decode + reconciliation in libdkgpu (SURVEY.md §8(b) plugin
     point 2)."""
@@ -1173,6 +1262,7 @@ class GpuScan:
         self.replay = None
         self.prepare_ms = {}
         self._handed = weakref.WeakValueDictionary()   # zero-copy checkpoint batches handed out (_detach_batches)
+        self._scan_readers = weakref.WeakSet()         # open ScanFileReaders (getScanFileBatches)
 
     def table_root(self):
         """tableRoot = dataPath.toUri().toString() (ActiveAddFilesIterator.java:251)."""
@@ -1397,9 +1487,15 @@ class GpuScan:
         applies."""
         return self.data_filter
 
+    def _close_scan_readers(self):
+        for rd in list(getattr(self, "_scan_readers", ())):
+            rd.close()
+        self._scan_readers = weakref.WeakSet()
+
     def run(self):
         """The device step: commit-tail keys + table, checkpoint decode, probe, selection (with an
         exchange: decode + routing, the exchange, then the probe of the rows the owners flagged)."""
+        self._synced = False
         if getattr(self, "owner", None) is not None:
             # the commit-tail exchange, dk_replay_run and the row exchanges, all in the library
             # (dk_replay_owner_run over the owner's dk_comm)
@@ -1412,6 +1508,7 @@ class GpuScan:
 
     def sync(self):
         check(lib().dk_replay_sync(self._rh))
+        self._synced = True
         cnt = (C.c_int64 * 5)()
         check(lib().dk_replay_counters(self._rh, cnt))
         self.metrics = ScanMetrics(*[int(x) for x in cnt])
@@ -1444,12 +1541,39 @@ class GpuScan:
                 out[name.value.decode()] = (avg.value, cnt.value)
         return out
 
+    def getScanFileBatches(self, engine, compact=True, batch_rows=None, window_rows=0, leaves=None):
+        """Scan.getScanFiles as bounded batches in the ParquetHandler reader's layout (dk_scan_next):
+        a generator of ScanFileBatch, in getScanFiles' order. compact=True yields only the selected
+        rows (selection None), compact=False every row with its selection. Runs the scan first when
+        it has no result yet; the counters (self.metrics) are final before the first batch."""
+        if self.replay is None:
+            self.prepare(engine)
+            self.replay = True
+            self._synced = False
+        if not getattr(self, "_synced", False):
+            self._detach_batches()
+            self._close_scan_readers()
+            self.run()
+            self.sync()
+        rd = ScanFileReader(self, compact, batch_rows, window_rows, leaves)
+        self._scan_readers.add(rd)
+        return self._scan_batches(rd)
+
+    @staticmethod
+    def _scan_batches(rd):
+        try:
+            yield from rd
+        finally:
+            rd.close()
+
     def getScanFiles(self, engine):
+        self._synced = False
         if self.replay is None:
             self.prepare(engine)
             self.replay = True
         else:
             self._detach_batches()          # the rerun reuses the pinned blocks earlier batches view
+            self._close_scan_readers()
         t0 = time.perf_counter()
         groups = scan_groups(len(self.ckpt_files or []))
         owner = getattr(self, "owner", None)
@@ -1564,6 +1688,7 @@ class GpuScan:
 
     def close(self):
         t0 = time.perf_counter()
+        self._close_scan_readers()
         if getattr(self, "_handed", None):
             self._detach_batches()
         t1 = time.perf_counter()

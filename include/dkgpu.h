@@ -396,6 +396,52 @@ int  dk_replay_ckpt_selection_bits(dk_replay* r, int32_t file, void* dst, int64_
 /* every checkpoint file's packed selection at dst + offsets[file] (one synchronisation for all);
  * the multi-GPU exchange writes its collective buffer with it */
 int  dk_replay_ckpt_selection_bits_all(dk_replay* r, void* dst, const int64_t* offsets, int32_t dst_on_device);
+/* ---- Scan-file batches: Scan.getScanFiles' CloseableIterator<FilteredColumnarBatch> over a finished
+ * replay (KA/Scan.java:101, KA/data/FilteredColumnarBatch.java:37-111), in the batch layout of
+ * dk_reader_next: validity bits, int32 offsets, value_offset, present = 0 for a leaf the file lacks,
+ * exactly as dk_batch_column documents. Batches are released with dk_batch_release.
+ *  Order      Appendix B's: the commit tail's rows (tail rows [0, dk_json_tail_checkpoint_row0)), then a
+ *             V2 JSON manifest's rows, then the checkpoint files in replay order, rows in file order. A
+ *             batch never spans two sources. dk_batch.file = the replay-order checkpoint file index,
+ *             -1 for the tail, -2 for JSON-manifest rows.
+ *  Row index  dk_batch.row_index is always set: the source row of each emitted row (the row within
+ *             the projected file for a checkpoint file; the row within the tail / within the manifest's
+ *             rows otherwise), which ties a compacted row back to its origin.
+ *  compact=1  only rows whose selection byte is non-zero are emitted; every batch of a source has
+ *             exactly batch_rows rows except that source's last; a source without a selected row
+ *             yields no batch; *selection = NULL.
+ *  compact=0  every row is emitted, at most batch_rows per batch; *selection = one byte per row of
+ *             the batch, in the batch's window memory (valid as long as the batch).
+ *  Leaves     any subset of the replay's projected leaves (the checkpoint's dk_parquet_open leaves;
+ *             without a checkpoint the commit tail's), by the same dotted names; an unknown leaf fails
+ *             the open.
+ *  Requires   a result: dk_replay_sync has returned 0 since the last dk_replay_run*, else the open
+ *             fails. Owner and exchange replays (dk_replay_set_owner / _set_exchange) are refused.
+ *  Lifetime   as dk_reader: single-threaded like a Kernel iterator; a batch stays valid until
+ *             dk_batch_release (from any thread), also after dk_scan_close; closing early is safe. The
+ *             reader must be closed before the next dk_replay_run* or dk_replay_free: dk_scan_next
+ *             after either fails (it never touches the replay's columns again), dk_scan_close stays
+ *             valid.
+ *  Overflow   a window whose values or chars of one leaf would not fit int32 offsets is halved; a
+ *             single batch that does not fit fails.
+ * All device work runs on the reader's own stream, ordered after the replay's; every transfer is a
+ * stream-ordered copy into pinned memory, one window (window_rows emitted rows) at a time. */
+typedef struct dk_scan_reader dk_scan_reader;
+typedef struct dk_scan_options {
+  int32_t compact;      /* 1: only selected rows are emitted (selection == NULL on every batch);
+                           0: every row plus a selection vector (the reference's FilteredColumnarBatch) */
+  int32_t batch_rows;   /* rows per batch; 0 = dk_config.parquet_batch_size */
+  int32_t window_rows;  /* emitted rows per host transfer window; 0 = about 1M, rounded to batches */
+} dk_scan_options;
+/* opt NULL: compact, default batch and window sizes */
+int  dk_replay_scan_open(dk_replay* r, const char* const* leaves, int32_t n_leaves, const dk_scan_options* opt,
+                         dk_scan_reader** out);
+/* *out = NULL once exhausted; selection may be NULL when the caller does not want it */
+int  dk_scan_next(dk_scan_reader* s, dk_batch** out, const uint8_t** selection);
+/* so far: [0] bytes copied from the device, [1] windows loaded, [2] rows and [3] batches emitted */
+int  dk_scan_stats(dk_scan_reader* s, int64_t out[4]);
+void dk_scan_close(dk_scan_reader* s);
+
 /* per-kernel average device time (us) over recorded runs (DK_FLAG_TIMING); names via index */
 /* hash(path)-owner exchange (multi-GPU "alltoall" mode; the repartition of actions by path that
  * delta-spark's Snapshot.scala:478-483 performs). After dk_replay_set_exchange(r, world, rank),
