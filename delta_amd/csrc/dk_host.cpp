@@ -62,6 +62,10 @@ void launch_json_canon(DJsonAction*, int, const uint8_t*, uint8_t*, uint32_t, DS
 void launch_slots_init(Slot*, uint64_t, hipStream_t);
 void launch_table_insert(const DJsonAction*, int, Slot*, uint64_t, hipStream_t);
 void launch_first_row(const uint8_t*, long long, int, unsigned long long*, hipStream_t);
+void launch_find_bytes(const uint8_t*, const int64_t*, const uint8_t*, long long, int, long long, const uint8_t*, int,
+                       unsigned long long*, hipStream_t);
+void lk_nonnull_rows(const uint8_t*, long long, int, long long, long long*, long long*, long long*, long long*, int64_t*,
+                     long long, hipStream_t);
 void launch_table_update(DJsonAction*, int, Slot*, uint64_t, const uint8_t*, DState*, hipStream_t);
 void launch_json_select(const DJsonAction*, int, const Slot*, uint64_t, const uint8_t*, uint8_t*, DState*, hipStream_t);
 void launch_stats_eval(const StatsRows&, const DSkipProg&, const SkScratch&, uint8_t*, DState*, hipStream_t);
@@ -1138,7 +1142,9 @@ struct dk_parquet {
   std::vector<std::unique_ptr<DBuf>> outbufs;
   std::vector<HostMirror> host;
   std::vector<HostCol> slice;   // dk_parquet_column_rows: one row range per column, offsets rebased
-  DBuf d_first;                 // dk_parquet_first_row result
+  DBuf d_first;                 // dk_parquet_first_row / dk_parquet_find_bytes result
+  DBuf d_needle;                // dk_parquet_find_bytes needle
+  DBuf d_lk_cnt, d_lk_base, d_lk_sums, d_lk_total, d_lk_rows;   // dk_parquet_nonnull_rows scratch and list
   DBuf d_expand;                // k_expand inputs (group prefix + ids)
   // slices for the pipelined prepare: per file its first page / column (n_files + 1 entries), the
   // compressed-page list and its segment / fragment prefixes, and an event after each file's copies
@@ -3048,6 +3054,76 @@ extern "C" int dk_parquet_first_row(dk_parquet* p, int32_t file, int32_t leaf, i
   HIPOK(hipStreamSynchronize(s));
   if (check_state(p)) return 1;
   *row = got == none ? -1 : (int64_t)got;
+  return 0;
+}
+
+// Set-transaction replay (LogReplay.loadLatestTransactionVersion, internal/replay/LogReplay.java:
+// 316-342, compares txn.appId of every non-null row with the application id): the first row at or
+// after from_row whose string equals the needle, found on the device.
+extern "C" int dk_parquet_find_bytes(dk_parquet* p, int32_t file, int32_t leaf, const uint8_t* needle, int32_t n,
+                                     int64_t from_row, int64_t* row) {
+  if (ensure_open(p)) return 1;
+  *row = -1;
+  if (file < 0 || file >= (int)p->files.size() || leaf < 0 || leaf >= (int)p->leaves.size()) return fail("bad column index");
+  if (n < 0 || (n > 0 && !needle)) return fail("dk_parquet_find_bytes: bad needle length");
+  if (from_row < 0 || from_row > p->files[file].num_rows) return fail("dk_parquet_find_bytes: from_row outside the file");
+  int ci = p->colmap[file][leaf];
+  if (ci < 0) return 0;
+  const DColumn& c = p->h_cols[ci];
+  if (c.phys != PT_BYTE_ARRAY || c.max_rep > 0)
+    return fail("dk_parquet_find_bytes: " + p->leaves[leaf] + " is not a non-repeated BYTE_ARRAY leaf");
+  if (c.null_only || from_row >= c.n_rows) return 0;
+  hipSetDevice(p->eng->cfg.device);
+  hipStream_t s = p->stream;
+  if (!p->d_first.p && p->d_first.alloc(8)) return 1;
+  if (n > 0 && upload(p->d_needle, needle, (size_t)n, s)) return 1;
+  const unsigned long long none = ~0ull;
+  HIPOK(hipMemcpyAsync(p->d_first.p, &none, 8, hipMemcpyHostToDevice, s));
+  launch_find_bytes(c.row_def, c.offs, c.chars, c.n_rows, c.max_def, from_row, p->d_needle.as<uint8_t>(), n,
+                    p->d_first.as<unsigned long long>(), s);
+  unsigned long long got = none;
+  HIPOK(hipMemcpyAsync(&got, p->d_first.p, 8, hipMemcpyDeviceToHost, s));
+  HIPOK(hipStreamSynchronize(s));
+  if (check_state(p)) return 1;
+  *row = got == none ? -1 : (int64_t)got;
+  return 0;
+}
+
+// Domain-metadata replay (LogReplay.loadDomainMetadataMap, LogReplay.java:356-378, visits every
+// non-null domainMetadata row): the rows at or after from_row whose level reaches min_def, listed
+// on the device; only the list crosses to the host.
+extern "C" int dk_parquet_nonnull_rows(dk_parquet* p, int32_t file, int32_t leaf, int32_t min_def, int64_t from_row,
+                                       int64_t* rows, int64_t cap, int64_t* n) {
+  if (ensure_open(p)) return 1;
+  *n = 0;
+  if (file < 0 || file >= (int)p->files.size() || leaf < 0 || leaf >= (int)p->leaves.size()) return fail("bad column index");
+  if (cap < 0 || (cap > 0 && !rows)) return fail("dk_parquet_nonnull_rows: bad capacity");
+  if (from_row < 0 || from_row > p->files[file].num_rows) return fail("dk_parquet_nonnull_rows: from_row outside the file");
+  int ci = p->colmap[file][leaf];
+  if (ci < 0) return 0;
+  const DColumn& c = p->h_cols[ci];
+  const long long m = c.n_rows - from_row;
+  if (m <= 0) return 0;
+  hipSetDevice(p->eng->cfg.device);
+  hipStream_t s = p->stream;
+  const long long nw = (m + 63) / 64;
+  const long long room = std::min<long long>(cap, m);
+  auto grow = [](DBuf& d, size_t bytes) { return (d.n < bytes || !d.p) ? d.alloc(bytes) : 0; };
+  if (grow(p->d_lk_cnt, (size_t)nw * 8) || grow(p->d_lk_base, (size_t)nw * 8) ||
+      grow(p->d_lk_sums, (size_t)enc_scan_blocks(nw) * 8 + 64) || grow(p->d_lk_total, 8) ||
+      (room > 0 && grow(p->d_lk_rows, (size_t)room * 8))) return 1;
+  lk_nonnull_rows(c.row_def + from_row, m, min_def, from_row, p->d_lk_cnt.as<long long>(), p->d_lk_base.as<long long>(),
+                  p->d_lk_sums.as<long long>(), p->d_lk_total.as<long long>(), p->d_lk_rows.as<int64_t>(), room, s);
+  long long total = 0;
+  HIPOK(hipMemcpyAsync(&total, p->d_lk_total.p, 8, hipMemcpyDeviceToHost, s));
+  HIPOK(hipStreamSynchronize(s));
+  if (check_state(p)) return 1;
+  const long long take = std::min(total, room);
+  if (take > 0) {
+    HIPOK(hipMemcpyAsync(rows, p->d_lk_rows.p, (size_t)take * 8, hipMemcpyDeviceToHost, s));
+    HIPOK(hipStreamSynchronize(s));
+  }
+  *n = total;
   return 0;
 }
 

@@ -7,6 +7,8 @@ Reference surface (paths under /root/reference/kernel/kernel-api/src/main/java/i
   Snapshot.getScanBuilder / ScanBuilder.build   Snapshot.java:69; internal/ScanBuilderImpl.java:77-86
   Scan.getScanFiles -> FilteredColumnarBatch Scan.java:101; internal/ScanImpl.java:120-186
   ScanMetrics counters                       internal/metrics/ScanMetrics.java:28-40
+  Snapshot.getLatestTransactionVersion       internal/SnapshotImpl.java:186; internal/replay/LogReplay.java:316-342
+  Snapshot.getDomainMetadataMap              internal/SnapshotImpl.java:153; internal/replay/LogReplay.java:356-378
 
 Log-segment selection is Kernel host logic the GPU engine does not replace; it is
 restated here because the JVM is absent. Decode, key building and reconciliation all run in
@@ -45,6 +47,8 @@ PM_LEAVES = ["protocol.minReaderVersion", "protocol.minWriterVersion",
              "metaData.configuration.key_value.key", "metaData.configuration.key_value.value",
              "metaData.createdTime"]
 SIDECAR_LEAVES = ["sidecar.path", "sidecar.sizeInBytes", "sidecar.modificationTime"]
+TXN_LEAVES = ["txn.appId", "txn.version"]
+DOMAIN_LEAVES = ["domainMetadata.domain", "domainMetadata.configuration", "domainMetadata.removed"]
 
 TIMING = 1
 
@@ -200,6 +204,29 @@ class ParquetSet:
         c = dk_column()
         check(lib().dk_parquet_column_rows(self._h, file_idx, self.leaves.index(leaf), row0, n, C.byref(c)))
         return Column(c, leaf)
+
+    def find_bytes(self, file_idx, leaf, needle: bytes, from_row=0):
+        """Smallest row >= from_row whose (non-null) string equals `needle` byte for byte, or -1
+        (device scan of a non-repeated BYTE_ARRAY leaf)."""
+        r = C.c_int64()
+        needle = bytes(needle)
+        check(lib().dk_parquet_find_bytes(self._h, file_idx, self.leaves.index(leaf), needle, len(needle), from_row,
+                                          C.byref(r)))
+        return r.value
+
+    def nonnull_rows(self, file_idx, leaf, min_def=1, from_row=0):
+        """Ascending int64 array of the rows >= from_row whose definition level is >= min_def (the
+        list is built on the device; only the list comes back)."""
+        li = self.leaves.index(leaf)
+        cap = 1024
+        while True:
+            rows = np.empty(cap, np.int64)
+            n = C.c_int64()
+            check(lib().dk_parquet_nonnull_rows(self._h, file_idx, li, min_def, from_row, rows.ctypes.data, cap,
+                                                C.byref(n)))
+            if n.value <= cap:
+                return rows[:n.value]
+            cap = n.value
 
     def columns(self, file_idx):
         """leaf -> Column, or None when the file lacks the leaf (all-null, NonExistentColumnReader)."""
@@ -688,6 +715,7 @@ class Snapshot:
         self.crc_info = None
         self._validated = False   # TableFeatures.validateReadSupportedTable ran in the P&M pass
         self._manifest = None
+        self._domain_metadata = None   # getDomainMetadataMap's result (the reference's Lazy)
 
     def getVersion(self):
         return self.log_segment.version
@@ -925,6 +953,124 @@ class Snapshot:
             # (where a cold load goes: footers, the open + device decode, the rows found and decoded)
             self.load_ms.update(checkpoint_pm_footers=(t_b - t_a) * 1e3, checkpoint_pm_decode=(t_c - t_b) * 1e3,
                                 checkpoint_pm_rows=(t_d - t_c) * 1e3)
+
+
+    # ---- the "first one wins" replays: set transactions and domain metadata ----
+    def _action_sources(self):
+        """LogSegment.allLogFilesReversed for a replay whose read schema holds neither add nor remove
+        (LogSegment.java:166-178; ActionsIterator.java:175-226): commit files newest first, then a V2
+        JSON manifest, then the checkpoint's Parquet files -- multi-part parts in descending name
+        order, a V2 Parquet manifest alone (sidecars are opened only for add / remove). Returns
+        (JSON files, Parquet files)."""
+        seg = self.log_segment
+        jsons = [d.path for d in reversed(seg.deltas)]
+        cks = seg.checkpoints
+        if not cks:
+            return jsons, []
+        if cks[0].kind == "v2":
+            if cks[0].path.endswith(".json"):
+                return jsons + [cks[0].path], []
+            return jsons, [cks[0].path]
+        return jsons, [f.path for f in sorted(cks, key=lambda f: os.path.basename(f.path), reverse=True)]
+
+    @staticmethod
+    def _json_actions(path, key):
+        """The non-null `key` actions of a commit file (or JSON manifest) in line order; only lines
+        naming the action are parsed."""
+        with open(path, "rb") as f:
+            raw = f.read()
+        mark = b'"' + key.encode() + b'"'
+        if mark not in raw:
+            return
+        for line in re.split(r"\r\n|\r|\n", raw.decode("utf-8", "replace")):
+            if '"' + key + '"' not in line:
+                continue
+            v = json.loads(line).get(key)
+            if v is not None:
+                yield v
+
+    @staticmethod
+    def _open_nonnull(engine, files, key_leaf, leaves):
+        """The row groups of `files` that can hold a non-null `key_leaf` (footer null counts), opened
+        and decoded with `leaves` only; files with no such row group are not opened. Returns the
+        set, or None when nothing is left."""
+        kept, groups = [], []
+        for f in files:
+            g = [i for i, k in enumerate(nonnull_row_groups(f, key_leaf)) if k]
+            if g:
+                kept.append(f)
+                groups.append(g)
+        return ParquetSet(engine, kept, leaves, groups=groups).decode() if kept else None
+
+    def getLatestTransactionVersion(self, engine, application_id):
+        """Snapshot.getLatestTransactionVersion (SnapshotImpl.java:186 -> LogReplay.
+        loadLatestTransactionVersion, LogReplay.java:316-342): the version of the first txn action,
+        in reverse log order, whose appId equals application_id; None when there is none. Commit
+        files are read on the host; a checkpoint file is searched on the device
+        (dk_parquet_find_bytes over txn.appId) and only the matching row's version comes back."""
+        from .actions import KernelException
+        jsons, parquets = self._action_sources()
+        for path in jsons:
+            for t in self._json_actions(path, "txn"):
+                if t.get("appId") == application_id:
+                    return int(t["version"])
+        needle = application_id.encode("utf-8")
+        for path in parquets:                      # one at a time: files after a match are not opened
+            ps = self._open_nonnull(engine, [path], "txn.appId", TXN_LEAVES)
+            if ps is None:
+                continue
+            try:
+                r = ps.find_bytes(0, "txn.appId", needle)
+                if r >= 0:
+                    v = _int_row(ps, 0, "txn.version", r, np.int64)
+                    if v is None:
+                        raise KernelException("txn action with a null version")
+                    return v
+            finally:
+                ps.close()
+        return None
+
+    def getDomainMetadataMap(self, engine):
+        """Snapshot.getDomainMetadataMap (SnapshotImpl.java:153 -> LogReplay.loadDomainMetadataMap,
+        LogReplay.java:356-378): domain -> {"domain", "configuration", "removed"}, the first action
+        seen per domain in reverse log order (DomainMetadataUtils.populateDomainMetadataMap,
+        DomainMetadataUtils.java:44-54; a removed = true action is kept like any other). Cached on
+        the snapshot. Checkpoint rows are listed on the device (dk_parquet_nonnull_rows) and only
+        those rows come back."""
+        from .actions import KernelException
+        if self._domain_metadata is not None:
+            return self._domain_metadata
+        out = {}
+
+        def put(domain, configuration, removed):
+            for name, v in (("domain", domain), ("configuration", configuration), ("removed", removed)):
+                if v is None:                       # DomainMetadata.fromColumnVector: requireNonNull
+                    raise KernelException("Field `%s` in `domainMetadata` is not nullable, but it is null" % name)
+            if domain not in out:
+                out[domain] = {"domain": domain, "configuration": configuration, "removed": bool(removed)}
+
+        jsons, parquets = self._action_sources()
+        for path in jsons:
+            for d in self._json_actions(path, "domainMetadata"):
+                put(d.get("domain"), d.get("configuration"), d.get("removed"))
+        ps = self._open_nonnull(engine, parquets, "domainMetadata.domain", DOMAIN_LEAVES)
+        if ps is not None:
+            try:
+                for fi in range(len(ps.paths)):
+                    rows = ps.nonnull_rows(fi, "domainMetadata.domain", 1)
+                    # runs of consecutive rows come back in one copy per leaf
+                    cut = np.flatnonzero(np.diff(rows) != 1) + 1
+                    for run in np.split(rows, cut) if len(rows) else []:
+                        r0, n = int(run[0]), len(run)
+                        dom, cfg, rem = (ps.column_rows(fi, lf, r0, n) for lf in DOMAIN_LEAVES)
+                        for i in range(n):
+                            put(*(None if c is None or not c.present or c.row_def[i] < c.max_def else
+                                  (bool(c.fixed[i]) if c.fixed is not None else c.string(i).decode("utf-8", "replace"))
+                                  for c in (dom, cfg, rem)))
+            finally:
+                ps.close()
+        self._domain_metadata = out
+        return out
 
 
 def _row(ps, fi, leaf, r):

@@ -145,6 +145,19 @@ int  dk_parquet_column(dk_parquet* p, int32_t file, int32_t leaf, dk_column* out
  * 220-314, which takes the first row whose protocol / metaData is non-null): index of the first row
  * of a decoded column with definition level >= min_def, found on the device; -1 when none. */
 int  dk_parquet_first_row(dk_parquet* p, int32_t file, int32_t leaf, int32_t min_def, int64_t* row);
+/* Set-transaction replay (LogReplay.loadLatestTransactionVersion, LogReplay.java:316-342): the
+ * smallest row >= from_row of a decoded non-repeated BYTE_ARRAY leaf whose value is non-null (full
+ * definition level) and byte-equal to needle[0..n), found on the device; -1 when none (and for a
+ * leaf the file lacks). n == 0 matches an empty non-null string only. A fixed-width or repeated
+ * leaf, from_row outside [0, num_rows] or n < 0 fails and launches nothing. */
+int  dk_parquet_find_bytes(dk_parquet* p, int32_t file, int32_t leaf, const uint8_t* needle, int32_t n,
+                           int64_t from_row, int64_t* row);
+/* Domain-metadata replay (LogReplay.loadDomainMetadataMap, LogReplay.java:356-378): the ascending
+ * list of rows >= from_row whose definition level is >= min_def, built on the device. *n = their
+ * total count, also when it exceeds cap; only the first cap are written to rows (the caller
+ * retries with a larger buffer or a later from_row). from_row outside [0, num_rows] fails. */
+int  dk_parquet_nonnull_rows(dk_parquet* p, int32_t file, int32_t leaf, int32_t min_def, int64_t from_row,
+                             int64_t* rows, int64_t cap, int64_t* n);
 /* D2H copy of rows [row0, row0+n) of one decoded column; row_offs / offs rebased to the slice
  * (valid until the next call for the same column or close). */
 int  dk_parquet_column_rows(dk_parquet* p, int32_t file, int32_t leaf, int64_t row0, int64_t n, dk_column* out);
