@@ -60,6 +60,11 @@ class dk_scan_options(C.Structure):
     _fields_ = [("compact", C.c_int32), ("batch_rows", C.c_int32), ("window_rows", C.c_int32)]
 
 
+class dk_data_options(C.Structure):
+    _fields_ = [("field_ids", C.c_void_p), ("predicate", C.c_void_p), ("dvs", C.c_void_p), ("dv_index", C.c_void_p),
+                ("filter", C.c_void_p), ("compact", C.c_int32), ("batch_rows", C.c_int32), ("window_rows", C.c_int32)]
+
+
 class dk_batch_column(C.Structure):
     _fields_ = [("present", C.c_int32), ("phys", C.c_int32), ("width", C.c_int32), ("max_def", C.c_int32),
                 ("max_rep", C.c_int32), ("rep_def", C.c_int32), ("n_values", C.c_int64), ("value_offset", C.c_int64),
@@ -143,7 +148,8 @@ EXPORTS = ["dk_last_error", "dk_version", "dk_engine_create", "dk_engine_destroy
            "dk_parsed_eval", "dk_parsed_free", "dk_comm_unique_id", "dk_comm_create", "dk_comm_create_callbacks",
            "dk_comm_create_local", "dk_comm_world", "dk_comm_rank", "dk_comm_allreduce_i64", "dk_comm_alltoallv",
            "dk_comm_abort", "dk_comm_last_run", "dk_comm_last_steps", "dk_comm_destroy", "dk_replay_owner_run", "dk_owner_protocol_run",
-           "dk_replay_scan_open", "dk_scan_next", "dk_scan_stats", "dk_scan_close"]
+           "dk_replay_scan_open", "dk_scan_next", "dk_scan_stats", "dk_scan_close",
+           "dk_data_compile", "dk_data_scan_open"]
 
 
 def lib(build_if_missing=True):
@@ -224,6 +230,9 @@ def lib(build_if_missing=True):
         "dk_scan_next": (C.c_int, [P, C.POINTER(C.POINTER(dk_batch)), C.POINTER(P)]),
         "dk_scan_stats": (C.c_int, [P, C.POINTER(I64)]),
         "dk_scan_close": (None, [P]),
+        "dk_data_compile": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(P)]),
+        "dk_data_scan_open": (C.c_int, [P, C.POINTER(C.c_char_p), I32, C.POINTER(C.c_char_p), I32,
+                                        C.POINTER(dk_data_options), C.POINTER(P)]),
         "dk_dv_load": (C.c_int, [P, C.c_char_p, C.POINTER(dk_dv_descriptor), I32, C.POINTER(P)]),
         "dk_dv_num_bits": (I64, [P, I32]),
         "dk_dv_bitmap": (C.c_int, [P, I32, P, I64, I32]),

@@ -336,6 +336,20 @@ struct StatsParsedRows {
   StatsRows js;
 };
 
+// Data-row filter (k_data_filter, dk_data_scan_open): the decoded rows of one data file, the columns
+// a dk_data_compile program reads (program field k = cols[k]; kind < 0: the file lacks the leaf, null
+// in every row), the file's dense deleted-row bitmap (k_dv_expand) and the map from decoded rows to
+// file rows (row groups pruned by the row-group predicate count, as _metadata.row_index counts them).
+struct DataRows {
+  int64_t n;
+  const TypedPath* cols;              // [program fields], device memory (null: no program)
+  const int64_t* rg;                  // n_rg pairs (first decoded row, its file row), ascending; device memory
+  int32_t n_rg;                       // 0: decoded row r is file row r
+  int32_t has_prog;
+  const unsigned long long* dv_bits;  // null: no DV
+  int64_t dv_nbits;                   // file rows >= dv_nbits are not deleted
+};
+
 // Per-lane scratch of the wide (> SK_NARROW paths) skipping kernels: path-major arrays of `lanes`
 // entries each (values, set words, typed kinds / scales / pointers); grids are sized to `lanes`.
 struct SkScratch {

@@ -941,7 +941,45 @@ struct PartCompiler {
   void push_bytes(int op, const std::string& b) { Op o; o.op = op; o.has_bytes = true; o.bytes = b; ops.push_back(o); }
 
   // element_at(add.partitionValues, 'name') [wrapped in partition_value(.., type)]: (phys, full type)
+  // data programs (dk_data_compile): a column of the physical read schema is a field; the map is
+  // the schema's primitive leaves (walk_schema: "complex" marks an array or a map)
+  const std::map<Path, std::string>* data_schema = nullptr;
+  std::map<std::string, Path> path_of;                     // data programs: a field's name -> its column
+  static std::string column_text(const Path& p) {          // Column.toString
+    std::string n = "column(";
+    for (size_t i = 0; i < p.size(); i++) n += (i ? ".`" : "`") + p[i] + "`";
+    return n + ")";
+  }
+  bool data_ref(const Ex& x, std::string* phys, std::string* type) {
+    if (x.k != Ex::COL) return false;
+    auto it = data_schema->find(x.names);
+    bool nested = it != data_schema->end() && it->second == "complex";
+    for (size_t n = 1; n < x.names.size() && !nested && it == data_schema->end(); n++) {
+      auto pre = data_schema->find(Path(x.names.begin(), x.names.begin() + n));
+      nested = pre != data_schema->end() && pre->second == "complex";
+    }
+    if (nested)
+      throw Unsupported{3, "Unsupported expression: " + column_text(x.names) + " is (inside) an array or a map: "
+                           "data filters read primitive columns only"};
+    if (it == data_schema->end())        // DefaultExpressionEvaluator.assertColumnExists (:681-686)
+      throw Unsupported{3, column_text(x.names) + " doesn't exist in input data schema"};
+    const std::string& t = it->second;
+    if (is_decimal(t)) {                 // precision > 18: FIXED_LEN_BYTE_ARRAY / BYTE_ARRAY in the file
+      const int prec = atoi(t.c_str() + (t.size() > 8 ? 8 : t.size()));
+      if (prec > 18)
+        throw Unsupported{3, "Unsupported expression: " + column_text(x.names) + " is a " + t +
+                             ": data filters read decimals of at most 18 digits"};
+    }
+    *phys = column_text(x.names);
+    *type = t;
+    return true;
+  }
   bool field_ref(const Ex& x, std::string* phys, std::string* type) {
+    if (data_schema) {
+      if (!data_ref(x, phys, type)) return false;
+      path_of[*phys] = x.names;
+      return true;
+    }
     const Ex* ea = &x;
     std::string t = "string";
     if (x.k == Ex::CALL && x.name == "PARTITION_VALUE") {
@@ -1198,7 +1236,8 @@ struct PartCompiler {
     const std::string ct = type_of(*left), lt = type_of(*right);
     if (!comparable(ct, lt)) unsupported_expr(n, ct, lt);
     std::string phys, tt;
-    if (!field_ref(*left, &phys, &tt) || right->k != Ex::LIT) { float_values_cmp(n, l0, r0); return; }
+    // (a data program's float / double column holds IEEE bits, not digit text: always two operands)
+    if (!field_ref(*left, &phys, &tt) || right->k != Ex::LIT || (data_schema && is_float(ct))) { float_values_cmp(n, l0, r0); return; }
     if (!is_float(ct) && !is_integral(ct)) refuse("comparison of " + ct + " with " + lt + " is not supported");
     auto cmp_code = [](const std::string& c) {
       return c == "<" ? PO_LT : c == "<=" ? PO_LE : c == ">" ? PO_GT : c == ">=" ? PO_GE : c == "=" ? PO_EQ : PO_NSEQ;
@@ -1431,13 +1470,98 @@ extern "C" int dk_part_compile(const char* predicate_json, dk_program** out) {
   return 0;
 }
 
+namespace {
+// parquet.field.id of each component of each primitive leaf of a StructType JSON (-1: none)
+void walk_field_ids(const JV& st, Path& prefix, std::vector<int32_t>& ids, std::map<Path, std::vector<int32_t>>& out) {
+  const JV* fields = st.get("fields");
+  if (!fields || fields->t != JV::ARR) return;
+  for (const JV& f : fields->a) {
+    const JV* n = f.get("name");
+    const JV* t = f.get("type");
+    if (!n || n->t != JV::STR || !t) continue;
+    long long id = -1;
+    if (const JV* md = f.get("metadata"))
+      if (const JV* v = md->get("parquet.field.id"))
+        if (v->t != JV::NUM || !parse_int64(v->s, &id) || id < 0 || id > INT_MAX) id = -1;
+    prefix.push_back(n->s);
+    ids.push_back((int32_t)id);
+    if (t->t == JV::STR) out[prefix] = ids;
+    else if (t->t == JV::OBJ && t->get("type") && t->get("type")->t == JV::STR && t->get("type")->s == "struct")
+      walk_field_ids(*t, prefix, ids, out);
+    prefix.pop_back();
+    ids.pop_back();
+  }
+}
+}  // namespace
+
+// The data filter of a scan (Scan.getRemainingFilter, or any predicate over the physical read schema)
+// as ExpressionHandler.getPredicateEvaluator(readSchema, predicate) takes it
+// (DefaultExpressionHandler -> DefaultPredicateEvaluator.java:42-72): the partition program's op set with
+// PO_FIELD = "column k of the row" (k_data_filter, dk_kernels.hip).
+extern "C" int dk_data_compile(const char* read_schema_json, const char* predicate_json, dk_program** out) {
+  if (!out) return dk::dk_fail("dk_data_compile: null out");
+  *out = nullptr;
+  JV sj, pj;
+  std::string err;
+  if (!parse_json(read_schema_json, sj, err)) return dk::dk_fail("dk_data_compile: read schema: " + err);
+  if (!parse_json(predicate_json, pj, err)) return dk::dk_fail("dk_data_compile: predicate: " + err);
+  std::vector<std::pair<Path, std::string>> leaves;
+  Path prefix;
+  if (sj.t != JV::OBJ || !walk_schema(sj, prefix, leaves, err)) return dk::dk_fail("dk_data_compile: " + (err.empty() ? "bad schema" : err));
+  std::map<Path, std::string> schema;
+  for (auto& l : leaves) schema[l.first] = l.second;
+  std::map<Path, std::vector<int32_t>> ids;
+  {
+    std::vector<int32_t> cur;
+    prefix.clear();
+    walk_field_ids(sj, prefix, cur, ids);
+  }
+  Ex root;
+  if (!to_expr(pj, root, err)) return dk::dk_fail("dk_data_compile: " + err);
+  std::unique_ptr<dk_program> P(new dk_program());
+  P->kind = DK_PROGRAM_DATA;
+  try {
+    PartCompiler C;
+    C.data_schema = &schema;
+    C.pred(root);
+    if (depth_of(C.ops, false) > kMaxStack) {
+      C.ops.clear();
+      C.used.clear();
+      C.types_full.clear();
+      const Ex b = rebalance(root);
+      C.pred(b);
+      if (depth_of(C.ops, false) > kMaxStack) refuse("data filter nests deeper than the device stack");
+    }
+    for (auto& u : C.used) {
+      const Path& path = C.path_of[u.first];
+      std::string dotted;
+      for (auto& c : path) dotted += (dotted.empty() ? "" : ".") + c;
+      P->field_type.push_back(pt_code(u.second));
+      P->fields.push_back(dotted);
+      P->field_path.push_back(path);
+      auto it = ids.find(path);
+      P->field_ids.push_back(it == ids.end() ? std::vector<int32_t>(path.size(), -1) : it->second);
+    }
+    finalize_ops(*P, C.ops, false);
+    P->stack = depth_of(C.ops, false);
+  } catch (const Unsupported& u) {
+    return compile_status(u);
+  } catch (const std::exception& e) {
+    return dk::dk_fail(std::string("dk_data_compile: ") + e.what());
+  }
+  if (P->pool.size() > (size_t)INT32_MAX) return dk::dk_fail("dk_data_compile: literals exceed 2 GiB");
+  *out = P.release();
+  return 0;
+}
+
 extern "C" void dk_program_free(dk_program* p) { delete p; }
 
 // JSON description of a compiled program: {"kind", "paths" | "fields", "stack", "ops": [[op, arg, lit], ...],
 // "pool": hex}; the skipping paths are what a caller projects as add.stats_parsed.<path>
 extern "C" int64_t dk_program_describe(const dk_program* p, char* buf, int64_t cap) {
   if (!p) return -1;
-  std::string s = "{\"kind\":" + std::to_string(p->kind) + ",\"stack\":" + std::to_string(p->stack);
+  std::string s = "{\"kind\":" + (p->kind == DK_PROGRAM_DATA ? std::string("\"data\"") : std::to_string(p->kind)) +
+                  ",\"stack\":" + std::to_string(p->stack);
   auto q = [](const std::string& x) {
     std::string o = "\"";
     for (unsigned char c : x) {
@@ -1452,6 +1576,14 @@ extern "C" int64_t dk_program_describe(const dk_program* p, char* buf, int64_t c
     for (size_t i = 0; i < p->paths.size(); i++) {
       s += (i ? "," : "") + std::string("{\"type\":") + std::to_string(p->path_type[i]) + ",\"path\":[";
       for (size_t k = 0; k < p->paths[i].size(); k++) s += (k ? "," : "") + q(p->paths[i][k]);
+      s += "]}";
+    }
+    s += "]";
+  } else if (p->kind == DK_PROGRAM_DATA) {
+    s += ",\"fields\":[";
+    for (size_t i = 0; i < p->field_path.size(); i++) {
+      s += (i ? "," : "") + std::string("{\"type\":") + std::to_string(p->field_type[i]) + ",\"path\":[";
+      for (size_t k = 0; k < p->field_path[i].size(); k++) s += (k ? "," : "") + q(p->field_path[i][k]);
       s += "]}";
     }
     s += "]";

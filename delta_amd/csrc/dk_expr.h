@@ -7,13 +7,18 @@
 #include <vector>
 
 struct dk_program {
-  int32_t kind = 0;                            // DK_PROGRAM_SKIPPING (0) / DK_PROGRAM_PARTITION (1)
+  int32_t kind = 0;                            // DK_PROGRAM_SKIPPING (0) / DK_PROGRAM_PARTITION (1) / DK_PROGRAM_DATA (2)
   // data skipping: the stats fields read from each row's stats (type code SK_*, name components)
   std::vector<int32_t> path_type;
   std::vector<std::vector<std::string>> paths;
   // partition pruning: the partition columns (type code PT_*, physical name)
   std::vector<int32_t> field_type;
   std::vector<std::string> fields;
+  // data rows (DK_PROGRAM_DATA, dk_data_compile): field k is the read-schema column field_path[k]
+  // (field_type[k] PT_*; fields[k] its dotted name), with the parquet.field.id of each component
+  // (-1: none) as the reader resolves leaves
+  std::vector<std::vector<std::string>> field_path;
+  std::vector<std::vector<int32_t>> field_ids;
   // postfix program and its pool (field / path names first, then literal bytes)
   std::vector<int32_t> op, arg;
   std::vector<int64_t> lit;

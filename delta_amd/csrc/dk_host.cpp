@@ -71,6 +71,7 @@ void launch_json_select(const DJsonAction*, int, const Slot*, uint64_t, const ui
 void launch_stats_eval(const StatsRows&, const DSkipProg&, const SkScratch&, uint8_t*, DState*, hipStream_t);
 void launch_stats_parsed(const StatsParsedRows&, const DSkipProg&, const SkScratch&, uint8_t*, DState*, hipStream_t);
 void launch_part_eval(const MapRows&, const DPartProg&, uint8_t*, DState*, hipStream_t);
+void launch_data_filter(const DataRows&, const DPartProg&, uint8_t*, hipStream_t);
 void launch_table_fp(const Slot*, uint32_t*, uint64_t, hipStream_t);
 void launch_probe_all(const ProbeSet&, const Slot*, const uint32_t*, uint64_t, const DJsonAction*, const uint8_t*, uint32_t, uint64_t,
                       int32_t*, unsigned int*, DState*, hipStream_t);
@@ -4023,8 +4024,8 @@ static int install_skip(DevSkip& d, const dk_program& src) {
   }
   return 0;
 }
-static int install_part(DevPart& d, const dk_program& src) {
-  if (src.kind != DK_PROGRAM_PARTITION) return fail("not a partition-pruning program");
+static int install_part(DevPart& d, const dk_program& src, int kind = DK_PROGRAM_PARTITION) {
+  if (src.kind != kind) return fail(kind == DK_PROGRAM_DATA ? "not a data-filter program (dk_data_compile)" : "not a partition-pruning program");
   d.prog = src;
   int64_t offs[8];
   const std::string img = program_image(src, offs);
@@ -6296,7 +6297,24 @@ struct dk_scan_reader : BatchOwner {
   DBuf d_rows, d_wcnt, d_wbase, d_sums, d_total, d_stage, d_ovf, d_cnt, d_ent;
   HBuf h_rng, h_tot;
   int64_t stats[4] = {0, 0, 0, 0};   // D2H bytes, windows, rows, batches
-  ~dk_scan_reader() override { if (ev) hipEventDestroy(ev); }
+  // data-row reader (dk_data_scan_open): its own decoded set instead of a replay's checkpoint; the
+  // first leaves.size() leaves of the set are the emitted ones, the rest only feed the filter
+  bool data = false;
+  dk_parquet* dp = nullptr;
+  std::vector<std::vector<std::pair<int64_t, int64_t>>> rgmap;   // per file, as dk_reader
+  std::vector<std::unique_ptr<DBuf>> d_dsel;                     // per file: one selection byte per decoded row
+  DevPart dprog;
+  DBuf d_dcols, d_drg;
+  dk_parquet* set() const { return data ? dp : rp->ck; }
+  // file's selection bytes in HBM (null: nothing selected)
+  const uint8_t* sel_of(int file) const {
+    if (data) return d_dsel[file]->as<uint8_t>();
+    return rp->probe[file].n_rows == 0 ? nullptr : rp->d_csel[file]->as<uint8_t>();
+  }
+  ~dk_scan_reader() override {
+    if (ev) hipEventDestroy(ev);
+    if (dp) dk_parquet_close(dp);
+  }
 };
 
 static void replay_drop_scans(dk_replay* r) {
@@ -6365,7 +6383,6 @@ extern "C" int dk_replay_scan_open(dk_replay* r, const char* const* leaves, int3
 // the rows a source emits: all of them, or (compact) the selected ones -- for a checkpoint file the
 // ordered list of its selected rows, built on the device
 static int scan_prepare_source(dk_scan_reader* s) {
-  dk_replay* r = s->rp;
   const ScanSrc& S = s->src[s->si];
   const hipStream_t st = s->own.s;
   if (S.file < 0) {
@@ -6376,12 +6393,12 @@ static int scan_prepare_source(dk_scan_reader* s) {
   }
   const int64_t n = S.b;
   if (!s->compact) { s->src_n = n; return 0; }
-  if (n == 0 || r->probe[S.file].n_rows == 0) { s->src_n = 0; return 0; }   // (no add.path: nothing selected)
+  if (n == 0 || !s->sel_of(S.file)) { s->src_n = 0; return 0; }   // (no add.path: nothing selected)
   if (n >= (1ll << 31) - 1) return fail("dk_scan_next: a checkpoint file of 2^31 rows or more");
   const long long nw = exp_sel_waves(n);
   if (grow(s->d_rows, (size_t)n * 4 + 64) || grow(s->d_wcnt, (size_t)nw * 8 + 64) || grow(s->d_wbase, (size_t)nw * 8 + 64) ||
       grow(s->d_sums, (size_t)enc_scan_blocks(nw) * 8 + 64) || grow(s->h_tot, 64)) return 1;
-  exp_sel_rows(r->d_csel[S.file]->as<uint8_t>(), n, s->d_wcnt.as<long long>(), s->d_wbase.as<long long>(),
+  exp_sel_rows(s->sel_of(S.file), n, s->d_wcnt.as<long long>(), s->d_wbase.as<long long>(),
                s->d_sums.as<long long>(), s->d_total.as<long long>(), s->d_rows.as<int32_t>(), st);
   HIPOK(hipMemcpyAsync(s->h_tot.data(), s->d_total.p, 8, hipMemcpyDeviceToHost, st));
   HIPOK(hipStreamSynchronize(st));
@@ -6394,8 +6411,7 @@ static size_t win_take(size_t& at, size_t n) { at = (at + 63) & ~(size_t)63; con
 
 // compact mode, checkpoint file: rows [j0, j0 + nr) of the file's selected-row list into a window
 static int gather_window(dk_scan_reader* s, RWin* w, int fi, int64_t j0, int64_t nr) {
-  dk_replay* r = s->rp;
-  dk_parquet* p = r->ck;
+  dk_parquet* p = s->set();
   const hipStream_t st = s->own.s;
   const size_t nl = s->leaves.size();
   w->file = fi; w->r0 = j0; w->leaf.assign(nl, WinLeaf());
@@ -6508,6 +6524,15 @@ static int gather_window(dk_scan_reader* s, RWin* w, int fi, int64_t j0, int64_t
   if (hsz > dsz) memset(H + dsz, 0, hsz - dsz);      // absent and all-null leaves: no device work
   HIPOK(hipStreamSynchronize(st));
   s->stats[0] += (int64_t)dsz;
+  if (s->data && !s->rgmap[fi].empty()) {            // decoded rows -> file rows (pruned row groups count)
+    const auto& m = s->rgmap[fi];
+    int64_t* ri = (int64_t*)(H + w->o_rowidx);
+    size_t k = 0;
+    for (int64_t i = 0; i < nr; i++) {
+      while (k + 1 < m.size() && m[k + 1].first <= ri[i]) k++;
+      ri[i] = m[k].second + (ri[i] - m[k].first);
+    }
+  }
   return 0;
 }
 
@@ -6605,7 +6630,7 @@ extern "C" int dk_scan_next(dk_scan_reader* s, dk_batch** out, const uint8_t** s
   if (selection) *selection = nullptr;
   if (!s) return fail("dk_scan_next: null reader");
   if (s->closed) return fail("dk_scan_next: the reader is closed");
-  if (!s->rp) return fail("dk_scan_next: the replay ran again or was freed (close the reader before either)");
+  if (!s->data && !s->rp) return fail("dk_scan_next: the replay ran again or was freed (close the reader before either)");
   hipSetDevice(s->eng->cfg.device);
   for (;;) {
     if (s->si >= s->src.size()) return 0;
@@ -6626,9 +6651,10 @@ extern "C" int dk_scan_next(dk_scan_reader* s, dk_batch** out, const uint8_t** s
       else if (s->compact) rc = gather_window(s, w, S.file, s->next, nr);
       else {
         WinCtx X;
-        X.p = s->rp->ck; X.fi = S.file; X.s = s->own.s; X.B = s->B; X.nl = s->leaves.size(); X.pleaf = &s->pleaf;
+        X.p = s->set(); X.fi = S.file; X.s = s->own.s; X.B = s->B; X.nl = s->leaves.size(); X.pleaf = &s->pleaf;
         X.row_index = true; X.want_sel = true;
-        X.d_sel = s->rp->probe[S.file].n_rows == 0 ? nullptr : s->rp->d_csel[S.file]->as<uint8_t>();
+        if (s->data) X.rgmap = &s->rgmap[S.file];
+        X.d_sel = s->sel_of(S.file);
         X.d_stage = &s->d_stage; X.d_ovf = &s->d_ovf; X.h_rng = &s->h_rng; X.d2h = &s->stats[0];
         rc = load_window(X, w, s->next, nr);
       }
@@ -6676,6 +6702,165 @@ extern "C" void dk_scan_close(dk_scan_reader* s) {
   s->closed = true;
   if (s->cur) { if (--s->cur->refs == 0) s->pool.push_back(s->cur); s->cur = nullptr; }
   reader_maybe_free(s, lk);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Data-row reader (dk_data_scan_open): Scan.transformPhysicalData with the DV and the
+// data filter applied per row on the device. The files are decoded like dk_reader_open's (row-group
+// pruning, field-id resolution), with the filter's columns appended to the projection; k_data_filter
+// writes each file's selection bytes once, at open; dk_scan_next then serves them exactly as it serves
+// a replay's checkpoint files (selected-row list + gathers, or whole windows + selection bytes).
+// ------------------------------------------------------------------------------------------------
+struct dk_dv_set;
+static int dv_set_bits(dk_dv_set* S, int32_t i, const unsigned long long** bits, int64_t* nbits);
+static int32_t dv_set_size(dk_dv_set* S);
+
+// program field type (PT_*) x the file's leaf -> how k_data_filter reads the values (TP_*), -1: cannot
+static int data_field_kind(int pt, const DColumn& c, const LeafM& L) {
+  const bool plain_int = L.dec_scale < 0 && !L.ts_unit;
+  switch (pt) {
+    case PT_LONG: return (c.phys == PT_INT64 || c.phys == PT_INT32) && plain_int ? TP_INT : -1;
+    case PT_INT: case PT_SHORT: case PT_BYTE: case PT_DATE: return c.phys == PT_INT32 && L.dec_scale < 0 ? TP_INT : -1;
+    case PT_BOOL: return c.phys == PT_BOOLEAN && c.width == 1 ? TP_INT : -1;
+    case PT_STRING: return c.phys == PT_BYTE_ARRAY ? TP_STR : -1;
+    case PT_DECIMAL: return (c.phys == PT_INT32 || c.phys == PT_INT64) && L.dec_scale >= 0 && L.dec_scale <= 38 ? TP_DEC : -1;
+    case PT_F32: return c.phys == PT_FLOAT ? TP_F32 : -1;
+    case PT_F64: return c.phys == PT_DOUBLE ? TP_F64 : -1;
+    case PT_TIMESTAMP:
+      if (c.phys == PT_INT64 && L.ts_unit == 2) return TP_INT;
+      if (c.phys == PT_INT64 && L.ts_unit == 1) return TP_MILLIS;
+      return c.phys == PT_INT96 ? TP_INT96 : -1;
+  }
+  return -1;
+}
+
+extern "C" int dk_data_scan_open(dk_engine* e, const char* const* paths, int32_t n_files, const char* const* leaves,
+                                 int32_t n_leaves, const dk_data_options* opt, dk_scan_reader** out) {
+  if (!out) return fail("dk_data_scan_open: null out");
+  *out = nullptr;
+  if (!e) return fail("null engine");
+  if (n_files < 0 || (n_files > 0 && !paths)) return fail("dk_data_scan_open: bad paths");
+  if (n_leaves < 0 || (n_leaves > 0 && !leaves)) return fail("dk_data_scan_open: bad leaves");
+  const dk_program* prog = opt ? opt->filter : nullptr;
+  if (prog && prog->kind != DK_PROGRAM_DATA) return fail("dk_data_scan_open: the filter is not a data-filter program (dk_data_compile)");
+  const int32_t n_dv = opt && opt->dvs ? dv_set_size(opt->dvs) : 0;
+  for (int32_t f = 0; opt && opt->dv_index && f < n_files; f++) {
+    const int32_t k = opt->dv_index[f];
+    if (k < 0) continue;
+    if (!opt->dvs) return fail("dk_data_scan_open: dv_index[" + std::to_string(f) + "] = " + std::to_string(k) + " without a deletion vector set");
+    if (k >= n_dv) return fail("dk_data_scan_open: dv_index[" + std::to_string(f) + "] = " + std::to_string(k) + " is out of range (" + std::to_string(n_dv) + " deletion vectors)");
+  }
+  hipSetDevice(e->cfg.device);
+  std::unique_ptr<dk_scan_reader> s(new dk_scan_reader());
+  s->eng = e; s->data = true;
+  s->compact = !opt || opt->compact != 0;
+  s->B = opt && opt->batch_rows > 0 ? opt->batch_rows : (e->cfg.parquet_batch_size > 0 ? e->cfg.parquet_batch_size : 1024);
+  if (opt && opt->window_rows > 0) s->W = opt->window_rows;
+  s->W = std::max<int64_t>(s->B, s->W / s->B * s->B);
+  // projection: the emitted leaves, then the filter's columns that are not among them
+  std::vector<std::string> all;
+  std::vector<int32_t> ids;
+  for (int i = 0; i < n_leaves; i++) {
+    if (!leaves[i]) return fail("dk_data_scan_open: null leaf");
+    s->leaves.push_back(leaves[i]); s->pleaf.push_back(i); s->jleaf.push_back(-1);
+    all.push_back(leaves[i]);
+    for (int d = 0; d < kMaxLeafDepth; d++) ids.push_back(opt && opt->field_ids ? opt->field_ids[(size_t)i * kMaxLeafDepth + d] : -1);
+  }
+  const int nf = prog ? (int)prog->fields.size() : 0;
+  std::vector<int> fleaf(nf, -1);                      // program field -> leaf of the set
+  bool any_id = opt && opt->field_ids;
+  for (int k = 0; k < nf; k++) {
+    for (size_t i = 0; i < all.size() && fleaf[k] < 0; i++) if (all[i] == prog->fields[k]) fleaf[k] = (int)i;
+    if (fleaf[k] >= 0) continue;
+    fleaf[k] = (int)all.size();
+    all.push_back(prog->fields[k]);
+    for (int d = 0; d < kMaxLeafDepth; d++) {
+      const int32_t id = d < (int)prog->field_ids[k].size() ? prog->field_ids[k][d] : -1;
+      any_id = any_id || id >= 0;
+      ids.push_back(id);
+    }
+  }
+  if (s->own.create()) return 1;
+  if (s->d_ovf.alloc(16) || s->d_total.alloc(64)) return 1;
+  // the predicate prunes row groups (best effort, never rows), as dk_reader_open
+  std::vector<std::vector<int32_t>> groups(n_files);
+  for (int32_t fi = 0; fi < n_files; fi++) {
+    FileM f;
+    f.path = paths[fi];
+    if (read_footer(f) || parse_footer(f)) return 1;
+    std::vector<uint8_t> keep(f.rgs.size() + 1, 1);
+    int32_t ng = 0;
+    if (opt && opt->predicate &&
+        dk_parquet_prune_row_groups(paths[fi], opt->predicate, keep.data(), (int32_t)keep.size(), &ng)) return 1;
+    int64_t at = 0, sel = 0;
+    std::vector<std::pair<int64_t, int64_t>> m;
+    bool pruned = false;
+    for (int32_t g = 0; g < (int32_t)f.rgs.size(); g++) {
+      if (keep[g]) { groups[fi].push_back(g); m.push_back({sel, at}); sel += f.rgs[g].num_rows; }
+      else pruned = true;
+      at += f.rgs[g].num_rows;
+    }
+    if (!pruned) m.clear();                            // decoded row r is file row r
+    s->rgmap.push_back(m);
+  }
+  std::vector<const char*> cl;
+  for (auto& l : all) cl.push_back(l.c_str());
+  if (parquet_open(e, paths, n_files, cl.data(), (int32_t)cl.size(), &groups, &s->dp, any_id ? ids.data() : nullptr)) return 1;
+  dk_parquet* p = s->dp;
+  if (dk_parquet_decode(p) || dk_parquet_sync(p)) return 1;
+  if (prog && install_part(s->dprog, *prog, DK_PROGRAM_DATA)) return 1;
+  // per file: the filter's columns, the row-group map, the DV -> one selection byte per decoded row
+  std::vector<TypedPath> cols((size_t)n_files * nf);
+  std::vector<int64_t> rg;
+  std::vector<size_t> rg_at(n_files, 0);
+  for (int32_t fi = 0; fi < n_files; fi++) {
+    if (p->files[fi].num_rows >= (1ll << 31) - 1) return fail("dk_data_scan_open: a data file of 2^31 rows or more");
+    for (int k = 0; k < nf; k++) {
+      TypedPath& T = cols[(size_t)fi * nf + k];
+      T = TypedPath{};
+      T.kind = -1;
+      const int ci = p->colmap[fi][fleaf[k]];
+      const int lx = p->leafidx[fi][fleaf[k]];
+      if (ci < 0 || lx < 0) continue;                  // the file lacks the leaf: null in every row
+      const DColumn& c = p->h_cols[ci];
+      const LeafM& L = p->files[fi].leaves[lx];
+      if (!c.present) continue;
+      const int kind = c.max_rep > 0 ? -1 : data_field_kind(prog->field_type[k], c, L);
+      if (kind < 0)
+        return fail("Error reading Parquet file: " + p->files[fi].path + ": column " + prog->fields[k] +
+                    " has a physical type the data filter cannot read as its Kernel type");
+      if (c.null_only) continue;                       // no value anywhere
+      if (kind == TP_STR ? !c.offs : !c.fixed) return fail("dk_data_scan_open: internal error: column " + prog->fields[k] + " has no values");
+      T.kind = kind; T.scale = kind == TP_DEC ? L.dec_scale : 0;
+      T.def = c.row_def; T.max_def = c.max_def; T.width = c.width;
+      T.vals = kind == TP_STR ? nullptr : c.fixed;
+      T.offs = kind == TP_STR ? c.offs : nullptr;
+      T.chars = kind == TP_STR ? c.chars : nullptr;
+    }
+    rg_at[fi] = rg.size();
+    for (auto& q : s->rgmap[fi]) { rg.push_back(q.first); rg.push_back(q.second); }
+  }
+  const hipStream_t st = s->own.s;
+  if (upload(s->d_dcols, cols.data(), cols.size() * sizeof(TypedPath), st) || upload(s->d_drg, rg.data(), rg.size() * 8, st)) return 1;
+  for (int32_t fi = 0; fi < n_files; fi++) {
+    const int64_t n = p->files[fi].num_rows;
+    s->d_dsel.emplace_back(new DBuf());
+    if (s->d_dsel.back()->alloc((size_t)n + 64)) return 1;
+    DataRows R{};
+    R.n = n;
+    R.cols = nf ? s->d_dcols.as<TypedPath>() + (size_t)fi * nf : nullptr;
+    R.has_prog = prog ? 1 : 0;
+    R.n_rg = (int32_t)s->rgmap[fi].size();
+    R.rg = R.n_rg ? s->d_drg.as<int64_t>() + rg_at[fi] : nullptr;
+    const int32_t dv = opt && opt->dv_index ? opt->dv_index[fi] : -1;
+    if (dv >= 0 && dv_set_bits(opt->dvs, dv, &R.dv_bits, &R.dv_nbits)) return 1;
+    if (R.dv_nbits <= 0) R.dv_bits = nullptr;          // an empty DV deletes nothing
+    launch_data_filter(R, s->dprog.P, s->d_dsel.back()->as<uint8_t>(), st);
+    s->src.push_back({fi, 0, n});
+  }
+  HIPOK(hipStreamSynchronize(st));                     // (the uploads read `cols` / `rg`)
+  *out = s.release();
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -6809,6 +6994,14 @@ struct dk_dv_set {
   DBuf d_bits;
   std::vector<int64_t> word0, nbits;    // per DV: first word, bits (max deleted row + 1; 0 = empty)
 };
+static int32_t dv_set_size(dk_dv_set* S) { return (int32_t)S->nbits.size(); }
+// DV i's dense bitmap in HBM (final: dk_dv_load returns with the set's stream drained)
+static int dv_set_bits(dk_dv_set* S, int32_t i, const unsigned long long** bits, int64_t* nbits) {
+  if (!S || i < 0 || i >= (int32_t)S->nbits.size()) return fail("bad deletion vector index");
+  *bits = S->d_bits.as<unsigned long long>() + S->word0[i];
+  *nbits = S->nbits[i];
+  return 0;
+}
 
 extern "C" int dk_dv_load(dk_engine* e, const char* table_root, const dk_dv_descriptor* dvs, int32_t n,
                           dk_dv_set** out) {

@@ -3872,9 +3872,49 @@ __device__ int java_fp_compare(double a, double b) {
   return sa == sb ? 0 : sa ? -1 : 1;
 }
 
-template <bool WIDE>
-__device__ int part_eval(const DPartProg& P, const MapRows& M, long long row, bool* err) {
+// The field source of part_eval: a partition program reads partitionValues map entries (part_field), a
+// data program (dk_data_compile) the decoded columns of a data file (data_field). `buf`: the stack
+// slot's text buffer (data programs only: a typed decimal's digits).
+__device__ __forceinline__ bool field_load(const DPartProg& P, const MapRows& M, long long row, int k, PVal* f, uint8_t*) {
+  return part_field(P, M, row, k, f);
+}
+
+// Column k of a data file's decoded row as the reference's readers hand it to the evaluator: null below
+// the leaf's definition level (or when the file lacks the leaf: NonExistentColumnReader); integral /
+// date / boolean values and timestamps in micros as integers -- INT64 millis times 1000
+// (TimestampConverters.TimestampMillisConverter, TimestampConverters.java:90-100), INT96 as
+// (julianDay - 2440588) * 86400000000 + nanosOfDay / 1000, the sub-microsecond nanos truncated
+// (DefaultKernelUtils.fromJulianDay, DefaultKernelUtils.java:53-57) --; strings and binary as their bytes
+// in the column's chars; INT32 / INT64 decimals as text; float / double as their IEEE bits (PO_FCMP2).
+__device__ __forceinline__ bool field_load(const DPartProg&, const DataRows& R, long long row, int k, PVal* f, uint8_t* buf) {
+  const TypedPath& T = R.cols[k];
+  f->kind = 0;
+  if (T.kind < 0 || T.def[row] < T.max_def) return true;
+  if (T.kind == TP_STR) {
+    const long long o0 = T.offs[row];
+    f->kind = 2; f->p = T.chars + o0; f->len = (int32_t)(T.offs[row + 1] - o0);
+    return true;
+  }
+  const uint8_t* v = T.vals + row * T.width;
+  const unsigned long long lo = T.width >= 4 ? ld_u32(v) : v[0];
+  const long long x = T.width >= 8 ? (long long)(lo | ((unsigned long long)ld_u32(v + 4) << 32))
+                    : T.width == 4 ? (long long)(int32_t)lo : (long long)lo;
+  f->kind = 1;
+  if (T.kind == TP_INT || T.kind == TP_F64) f->v = x;
+  else if (T.kind == TP_F32) f->v = (long long)lo;
+  else if (T.kind == TP_MILLIS) f->v = (long long)((unsigned long long)x * 1000ull);
+  else if (T.kind == TP_INT96) f->v = ((long long)(int32_t)ld_u32(v + 8) - 2440588ll) * 86400000000ll + x / 1000;
+  else { f->kind = 4; f->p = buf; f->len = dec_text(x, T.scale, buf); }
+  return true;
+}
+
+template <class Src> struct FieldBuf { static constexpr int bytes = 1; };
+template <> struct FieldBuf<DataRows> { static constexpr int bytes = 28; };   // dec_text: <= 26 bytes
+
+template <bool WIDE, class Src>
+__device__ int part_eval(const DPartProg& P, const Src& M, long long row, bool* err) {
   PVal st[PP_STACK];
+  uint8_t fbuf[FieldBuf<Src>::bytes > 1 ? PP_STACK * FieldBuf<Src>::bytes : 1];
   int sp = 0;
   for (int i = 0; i < P.n_ops; i++) {
     const int op = P.op[i];
@@ -3882,7 +3922,7 @@ __device__ int part_eval(const DPartProg& P, const MapRows& M, long long row, bo
       if (sp >= PP_STACK) return -1;
       PVal& t = st[sp++];
       if (op == PO_FIELD) {
-        if (!part_field(P, M, row, P.arg[i], &t)) { *err = true; return -1; }
+        if (!field_load(P, M, row, P.arg[i], &t, fbuf + (FieldBuf<Src>::bytes > 1 ? (sp - 1) * FieldBuf<Src>::bytes : 0))) { *err = true; return -1; }
       } else if (op == PO_LIT_INT) {
         t.kind = 1; t.v = P.lit[i];
       } else if (op == PO_LIT_NULL) {
@@ -4065,6 +4105,37 @@ __global__ __launch_bounds__(NT) void k_part_eval(MapRows M, const DPartProg P,
 __global__ __launch_bounds__(NT) void k_part_eval_wide(MapRows M, const DPartProg P,
                                                        uint8_t* __restrict__ sel, DState* __restrict__ st) {
   part_eval_rows<true>(M, P, sel, st);
+}
+
+// Data rows (dk_data_scan_open): sel[r] = the row's file row is not in the deletion vector and the data
+// program is TRUE for it -- DefaultPredicateEvaluator.eval (DefaultPredicateEvaluator.java:42-72) over
+// the selection Scan.transformPhysicalData builds from the DV (Scan.java:176-199). One lane per decoded
+// row; every row evaluates the whole program (no short-circuit, as the reference); one byte stored per
+// row. A program that does not evaluate (it cannot: the host compiled it) selects nothing.
+template <bool WIDE>
+__device__ __forceinline__ void data_filter_rows(const DataRows& R, const DPartProg& P, uint8_t* __restrict__ sel) {
+  for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < R.n;
+       r += (long long)gridDim.x * blockDim.x) {
+    long long ri = r;
+    if (R.n_rg > 0) {                                   // the last row group starting at or before r
+      int a = 0, b = R.n_rg - 1;
+      while (a < b) { const int m = (a + b + 1) >> 1; if (R.rg[2 * m] <= r) a = m; else b = m - 1; }
+      ri = R.rg[2 * a + 1] + (r - R.rg[2 * a]);
+    }
+    bool keep = !(R.dv_bits && ri < R.dv_nbits && ((R.dv_bits[ri >> 6] >> (ri & 63)) & 1ull));
+    if (R.has_prog) {
+      bool err = false;
+      const int res = part_eval<WIDE>(P, R, r, &err);
+      keep = keep && !err && res == 1;
+    }
+    sel[r] = keep ? 1 : 0;
+  }
+}
+__global__ __launch_bounds__(NT) void k_data_filter(DataRows R, const DPartProg P, uint8_t* __restrict__ sel) {
+  data_filter_rows<false>(R, P, sel);
+}
+__global__ __launch_bounds__(NT) void k_data_filter_wide(DataRows R, const DPartProg P, uint8_t* __restrict__ sel) {
+  data_filter_rows<true>(R, P, sel);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -4966,6 +5037,13 @@ void launch_part_eval(const MapRows& M, const DPartProg& P, uint8_t* sel, DState
   const unsigned grid = (unsigned)(want < 2048 ? want : 2048);
   if (P.wide) hipLaunchKernelGGL(k_part_eval_wide, dim3(grid), dim3(NT), 0, s, M, P, sel, st);
   else hipLaunchKernelGGL(k_part_eval, dim3(grid), dim3(NT), 0, s, M, P, sel, st);
+}
+void launch_data_filter(const DataRows& R, const DPartProg& P, uint8_t* sel, hipStream_t s) {
+  if (R.n <= 0) return;
+  const long long want = (R.n + NT - 1) / NT;
+  const unsigned grid = (unsigned)(want < 2048 ? want : 2048);
+  if (R.has_prog && P.wide) hipLaunchKernelGGL(k_data_filter_wide, dim3(grid), dim3(NT), 0, s, R, P, sel);
+  else hipLaunchKernelGGL(k_data_filter, dim3(grid), dim3(NT), 0, s, R, P, sel);
 }
 // First row whose definition level reaches min_def (LogReplay.loadTableProtocolAndMetadata takes
 // the first non-null protocol / metaData row, internal/replay/LogReplay.java:247-296): a grid-stride

@@ -174,3 +174,11 @@ class GpuExpressionHandler:
         if rc:
             programs._raise(rc, UnsupportedSkipping)
         return GpuPredicateEvaluator(self.engine, programs.Program(h))
+
+    def getDataPredicateEvaluator(self, read_schema, predicate):
+        """getPredicateEvaluator(readSchema, predicate) for data batches (DefaultPredicateEvaluator.java:
+        42-72): the compiled program that GpuScan.readData / dk_data_scan_open evaluate per row on the
+        device. read_schema: the scan state's physical read schema (JSON text or dict); predicate: a
+        Kernel Predicate over its columns."""
+        from . import programs
+        return programs.compile_data_filter(predicate, read_schema)

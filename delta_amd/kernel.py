@@ -26,8 +26,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (MAX_LEAF_DEPTH, Column, DkError, check, dk_batch, dk_column, dk_config, dk_dv_descriptor,
-                   dk_read_options, dk_rg_filter, dk_scan_options, lib)
+from ._lib import (MAX_LEAF_DEPTH, Column, DkError, check, dk_batch, dk_column, dk_config, dk_data_options,
+                   dk_dv_descriptor, dk_read_options, dk_rg_filter, dk_scan_options, lib)
 
 ADD_LEAVES = ["add.path", "add.partitionValues.key_value.key", "add.partitionValues.key_value.value",
               "add.size", "add.modificationTime", "add.dataChange",
@@ -463,6 +463,171 @@ def read_scan_data(engine, scan, leaves):
             k += 1
     if dvs is not None:
         dvs.close()
+
+
+@dataclass
+class DataBatch:
+    """One batch of GpuScan.readData / DataReader: rows of one data file in the ParquetHandler reader's
+    layout (BatchColumn). selection: bool per row, or None in compact mode (every row of the batch
+    survived the deletion vector and the filter); row_index: the file row of each row;
+    partition_values: the scan file's add.partitionValues (None outside a scan)."""
+    path: str
+    file_index: int
+    columns: dict
+    selection: np.ndarray | None
+    row_index: np.ndarray
+    partition_values: dict | None = None
+
+    @property
+    def size(self):
+        return len(self.row_index)
+
+
+class DataReader:
+    """dk_data_scan_open over data files: deletion vectors and a compiled data filter
+    (programs.compile_data_filter) applied per row on the device, batches through dk_scan_next.
+    dvs: a DeletionVectors set with dv_index[f] = file f's DV in it (-1: none); predicate: a packed
+    row-group filter (dk_rg_filter) as ParquetReader takes it; field_ids: leaf -> ids, as ParquetReader."""
+
+    def __init__(self, engine, paths, leaves, filter=None, dvs=None, dv_index=None, compact=True, batch_rows=None,
+                 window_rows=0, predicate=None, field_ids=None):
+        self.paths = list(paths)
+        self.leaves = list(leaves)
+        opt = dk_data_options()
+        self._keep = [filter, dvs, predicate]
+        if field_ids:
+            ids = np.full(max(1, len(self.leaves)) * MAX_LEAF_DEPTH, -1, np.int32)
+            for i, leaf in enumerate(self.leaves):
+                for d, v in enumerate((field_ids.get(leaf) or [])[:MAX_LEAF_DEPTH]):
+                    ids[i * MAX_LEAF_DEPTH + d] = -1 if v is None else v
+            self._keep.append(ids)
+            opt.field_ids = ids.ctypes.data
+        opt.predicate = C.cast(C.byref(predicate), C.c_void_p) if predicate is not None else None
+        opt.dvs = dvs._h if dvs is not None else None
+        if dv_index is not None:
+            dvi = np.ascontiguousarray(dv_index, dtype=np.int32)
+            if dvi.size != len(self.paths):
+                raise ValueError("dv_index needs one entry per file")
+            self._keep.append(dvi)
+            opt.dv_index = dvi.ctypes.data if dvi.size else None
+        opt.filter = filter.handle if filter is not None else None
+        opt.compact, opt.batch_rows, opt.window_rows = (1 if compact else 0), int(batch_rows or 0), int(window_rows or 0)
+        self._h = C.c_void_p()
+        check(lib().dk_data_scan_open(engine._h, _cstrs(self.paths), len(self.paths), _cstrs(self.leaves),
+                                      len(self.leaves), C.byref(opt), C.byref(self._h)))
+
+    def next_raw(self):
+        """(dk_batch pointer, selection address or None), or None at the end."""
+        out, sel = C.POINTER(dk_batch)(), C.c_void_p()
+        check(lib().dk_scan_next(self._h, C.byref(out), C.byref(sel)))
+        return (out, sel.value) if out else None
+
+    @staticmethod
+    def release(raw):
+        lib().dk_batch_release(raw)
+
+    def stats(self):
+        """bytes copied from the device, windows loaded, rows and batches emitted so far."""
+        st = (C.c_int64 * 4)()
+        check(lib().dk_scan_stats(self._h, st))
+        return dict(d2h_bytes=int(st[0]), windows=int(st[1]), rows=int(st[2]), batches=int(st[3]))
+
+    def batch(self, raw, sel):
+        b = raw.contents
+        n = int(b.n_rows)
+        return DataBatch(self.paths[b.file], int(b.file),
+                         {leaf: BatchColumn(b.cols[i], n, leaf) for i, leaf in enumerate(self.leaves)},
+                         _np_view(sel, n, np.uint8).astype(bool) if sel else None,
+                         _np_view(b.row_index, n, np.int64).copy())
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        got = self.next_raw()
+        if got is None:
+            raise StopIteration
+        try:
+            return self.batch(*got)
+        finally:
+            lib().dk_batch_release(got[0])
+
+    def close(self):
+        if self._h:
+            lib().dk_scan_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _physical_predicate(pred, logical, physical):
+    """A predicate over logical column names rewritten to the physical names of the same fields
+    (column mapping: physical_struct keeps the logical schema's field order at every level). A column
+    the logical schema lacks is left as it is: the compiler reports it."""
+    from . import schema
+    from .expressions import Column as ExprColumn, Predicate
+
+    def rename(names):
+        out, ls, ps = [], logical, physical
+        for i, n in enumerate(names):
+            if not isinstance(ls, schema.Struct):
+                return names
+            idx = [j for j, f in enumerate(ls.fields) if f.name == n] or \
+                  [j for j, f in enumerate(ls.fields) if f.name.lower() == n.lower()]
+            if not idx:
+                return names
+            out.append(ps.fields[idx[0]].name)
+            ls, ps = ls.fields[idx[0]].type, ps.fields[idx[0]].type
+        return tuple(out)
+
+    def rw(e):
+        if isinstance(e, ExprColumn):
+            return ExprColumn(*rename(e.names))
+        if isinstance(e, Predicate):
+            return Predicate(e.name, *[rw(c) for c in e.children])
+        return e
+    return rw(pred)
+
+
+def _leaf_field_ids(physical, leaf):
+    """parquet.field.id of each struct-level component of a dotted physical leaf (None where the
+    schema gives none; components below an array or a map resolve by name)."""
+    from . import schema
+    ids, st = [], physical
+    for n in leaf.split("."):
+        f = next((f for f in st.fields if f.name == n), None) if isinstance(st, schema.Struct) else None
+        if f is None:
+            ids.append(None)
+            st = None
+            continue
+        fid = f.metadata.get(schema.PARQUET_FIELD_ID_KEY)
+        ids.append(fid if isinstance(fid, int) and not isinstance(fid, bool) else None)
+        st = f.type
+    return ids
+
+
+def _partition_values_of(data, r):
+    """add.partitionValues of scan-file row r as a dict (a null value -> None; a null map -> {})."""
+    k = data["add.partitionValues.key_value.key"]
+    v = data["add.partitionValues.key_value.value"]
+    if k is None or not k.present or k.row_offs is None:
+        return {}
+    out = {}
+    for e in range(int(k.row_offs[r]), int(k.row_offs[r + 1])):
+        if k.entry_def[e] < k.max_def:
+            continue
+        out[k.string(e).decode()] = v.string(e).decode() if v.entry_def[e] == v.max_def else None
+    return out
 
 
 class JsonTail:
@@ -1632,6 +1797,52 @@ class GpuScan:
         """ScanImpl.getRemainingFilter (:221-223): the data filter, which skipping never fully
         applies."""
         return self.data_filter
+
+    def readData(self, engine, leaves, filter="remaining", compact=True, batch_rows=None, window_rows=0):
+        """Scan.transformPhysicalData with the predicate evaluated on the device (Scan.java:147-230;
+        getPredicateEvaluator(schema, predicate).eval(batch, selection), DefaultPredicateEvaluator.java:
+        42-72): every selected scan file is decoded on the GPU, its deletion vector and `filter` decide
+        each row there, and only the surviving rows (compact=True) cross to the host. A generator of
+        DataBatch in scan-file order. leaves: physical Parquet leaf paths to emit; filter: "remaining"
+        (getRemainingFilter()), a Predicate over the table's logical columns, or None."""
+        from urllib.parse import unquote
+        from . import programs, schema
+        state = self.getScanState(engine)
+        pred = self.getRemainingFilter() if isinstance(filter, str) and filter == "remaining" else filter
+        physical = schema.parse(state["physicalSchemaString"])
+        mapped = schema.column_mapping_mode(state["configuration"]) != "none"
+        prog = None
+        if pred is not None:
+            if mapped:
+                pred = _physical_predicate(pred, schema.parse(state["logicalSchemaString"]), physical)
+            prog = programs.compile_data_filter(pred, state["physicalDataReadSchemaString"])
+        root = self.table_root()
+        files = []
+        for b in self.getScanFiles(engine):
+            for r in b.selected_rows():
+                r = int(r)
+                files.append((b.data["add.path"].string(r).decode(), _dv_of(b.data, r), _partition_values_of(b.data, r)))
+        with_dv = [dv for _, dv, _ in files if dv is not None]
+        dvs = DeletionVectors(engine, root, with_dv) if with_dv else None
+        dv_index, local, k = [], [], 0
+        for path, dv, _ in files:
+            full = path if re.match(r"^[A-Za-z][A-Za-z0-9+.-]*:", path) else root.rstrip("/") + "/" + unquote(path)
+            local.append(full[5:] if full.startswith("file:") else full)
+            dv_index.append(-1 if dv is None else k)
+            k += dv is not None
+        ids = {leaf: _leaf_field_ids(physical, leaf) for leaf in leaves} if mapped else None
+        rd = DataReader(engine, local, leaves, filter=prog, dvs=dvs, dv_index=dv_index, compact=compact,
+                        batch_rows=batch_rows, window_rows=window_rows, field_ids=ids)
+        try:
+            for batch in rd:
+                batch.path, batch.partition_values = files[batch.file_index][0], files[batch.file_index][2]
+                yield batch
+        finally:
+            rd.close()
+            if dvs is not None:
+                dvs.close()
+            if prog is not None:
+                prog.close()
 
     def _close_scan_readers(self):
         for rd in list(getattr(self, "_scan_readers", ())):

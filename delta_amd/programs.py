@@ -178,6 +178,23 @@ def compile_partition(pred, fields) -> Program:
     return Program(h)
 
 
+class UnsupportedDataFilter(DkError):
+    """A data filter this engine build cannot compile (the reference's evaluator would run it)."""
+
+
+def compile_data_filter(predicate, read_schema) -> Program:
+    """dk_data_compile: a Kernel Predicate over the columns of the PHYSICAL read schema (StructType JSON
+    text or dict, as getScanState's physicalDataReadSchemaString) -> the program dk_data_scan_open
+    evaluates per data row. UnsupportedExpression (status 3): an array / map column, a column the schema
+    lacks, operand types that do not compare, a decimal of more than 18 digits."""
+    schema = read_schema if isinstance(read_schema, str) else json.dumps(read_schema)
+    h = C.c_void_p()
+    rc = lib().dk_data_compile(schema.encode(), json.dumps(_expr_json(predicate)).encode(), C.byref(h))
+    if rc:
+        _raise(rc, UnsupportedDataFilter)
+    return Program(h)
+
+
 def check_status(rc):
     if rc != 0:
         raise DkError(lib().dk_last_error().decode("utf-8", "replace"))

@@ -308,9 +308,21 @@ typedef struct dk_program dk_program;
 #define DK_PROGRAM_PARTITION 1
 int  dk_skip_compile(const char* stats_schema_json, const char* predicate_json, dk_program** out);
 int  dk_part_compile(const char* predicate_json, dk_program** out);
+/* dk_data_compile: a predicate over the rows of data files -- Scan.getRemainingFilter, or any predicate
+ * over the scan state's physical read schema -- as ExpressionHandler.getPredicateEvaluator(readSchema,
+ * predicate) takes it (KD/internal/expressions/DefaultPredicateEvaluator.java:42-72). read_schema_json is
+ * Kernel StructType JSON of the PHYSICAL read schema; {"col": [...]} names one of its columns, a nested
+ * struct field by path. Same predicate grammar and type rules as dk_part_compile (without ELEMENT_AT /
+ * PARTITION_VALUE); the program runs per decoded row on the device (dk_data_scan_open). Status 3, with
+ * the column named: a column that is, or lies inside, an array or a map; a column the schema lacks
+ * ("column(`x`) doesn't exist in input data schema"); operand types that do not compare; a decimal
+ * column of more than 18 digits (stored as FIXED_LEN_BYTE_ARRAY / BYTE_ARRAY). */
+#define DK_PROGRAM_DATA 2
+int  dk_data_compile(const char* read_schema_json, const char* predicate_json, dk_program** out);
 /* JSON description: {"kind", "stack", "paths": [{"type", "path": [...]}] | "fields": [{"type", "name"}],
  * "ops": [[op, arg, lit], ...], "pool": hex}; returns its length (writes at most cap - 1 bytes + NUL).
- * The paths are what a caller projects as the typed add.stats_parsed.<path> leaves. */
+ * The paths are what a caller projects as the typed add.stats_parsed.<path> leaves. A data program
+ * has "kind": "data" and "fields": [{"type", "path": [...]}] (the read-schema columns it reads). */
 int64_t dk_program_describe(const dk_program* p, char* buf, int64_t cap);
 void dk_program_free(dk_program* p);
 
@@ -454,6 +466,34 @@ int  dk_scan_next(dk_scan_reader* s, dk_batch** out, const uint8_t** selection);
 /* so far: [0] bytes copied from the device, [1] windows loaded, [2] rows and [3] batches emitted */
 int  dk_scan_stats(dk_scan_reader* s, int64_t out[4]);
 void dk_scan_close(dk_scan_reader* s);
+
+/* ---- Data-row batches: Scan.transformPhysicalData with the predicate evaluated on the device
+ * (KA/Scan.java:147-230; ExpressionHandler.getPredicateEvaluator(schema, predicate).eval(batch,
+ * existingSelection), DefaultPredicateEvaluator.java:42-72). The data files are decoded on the reader's
+ * own stream as dk_reader_open decodes them; per file one kernel writes a selection byte per decoded row,
+ * sel = !(DV bit of the row's file row) && filter is TRUE, and the batches come out of dk_scan_next in
+ * the contract documented above: compact = 1 emits only surviving rows in full batches (a file without a
+ * survivor yields no batch), compact = 0 every row plus its selection bytes; dk_batch.file is the input
+ * file index; dk_batch.row_index is always set to the FILE row of each row (row groups the row-group
+ * predicate pruned count, as _metadata.row_index counts them). Consumed and closed with dk_scan_next /
+ * dk_scan_stats / dk_scan_close / dk_batch_release.
+ *  filter   a dk_data_compile program (copied). Its columns resolve to file leaves by field id, then
+ *           name, then case-insensitive name, like the reader's leaves; they are decoded also when they
+ *           are not among `leaves`, and are not emitted then. A column a file lacks is null in every
+ *           row. A column whose file type cannot hold the program's type fails the open.
+ *  dvs      the scan files' deletion vectors (dk_dv_load); dv_index[f] is file f's DV in the set, -1 none.
+ * Errors, all failing the open before anything is launched: a program whose kind is not DK_PROGRAM_DATA,
+ * dv_index out of range, dvs == NULL with an index >= 0. */
+typedef struct dk_data_options {
+  const int32_t* field_ids;        /* as dk_read_options */
+  const dk_rg_filter* predicate;   /* row-group pruning, as dk_read_options; NULL = none */
+  dk_dv_set* dvs;                  /* NULL = no file has a DV */
+  const int32_t* dv_index;         /* per file: index into dvs, or -1 */
+  const dk_program* filter;        /* dk_data_compile; NULL = no predicate */
+  int32_t compact, batch_rows, window_rows;   /* as dk_scan_options */
+} dk_data_options;
+int  dk_data_scan_open(dk_engine* e, const char* const* paths, int32_t n_files, const char* const* leaves,
+                       int32_t n_leaves, const dk_data_options* opt, dk_scan_reader** out);
 
 /* per-kernel average device time (us) over recorded runs (DK_FLAG_TIMING); names via index */
 /* hash(path)-owner exchange (multi-GPU "alltoall" mode; the repartition of actions by path that
