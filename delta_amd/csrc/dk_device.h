@@ -15,7 +15,11 @@ struct DChunk {
   int64_t dict_hash_off; // key columns: offset of this chunk's dictionary entries in DColumn.dhash
 };
 
-enum : int32_t { PF_DICT = 1 };
+// PF_POS: a BYTE_ARRAY data page whose chars are placed through its position slots (PLAIN: k_pos_*, the
+// delta byte-array encodings: k_delta_lengths); PF_SLOT64: a fixed-width data page whose values are in
+// the 64-bit scratch (DELTA_BINARY_PACKED: k_delta_decode, BYTE_STREAM_SPLIT: k_bss_gather). Both are set
+// by the host plan, so k_tile_decode tests one bit where it tested one encoding.
+enum : int32_t { PF_DICT = 1, PF_POS = 2, PF_SLOT64 = 4 };
 enum : int32_t { PS_OK = 0, PS_BAD_HEADER = 1, PS_BAD_LEVELS = 2, PS_BAD_VALUES = 3,
                  PS_UNSUPPORTED = 4, PS_BAD_DICT = 5, PS_BAD_SNAPPY = 6 };
 
@@ -29,7 +33,8 @@ struct DPage {
   int64_t data_off;      // offset of the page body in the packed chunk image
   int64_t unc_off;       // offset into the decompression arena, -1 = read in place (input)
   // totals (k_tile_scan1 / k_tile_scan2: sums over the page's level tiles)
-  int32_t n_rows, n_entries, n_values, pad;
+  int32_t n_rows, n_entries, n_values;
+  int32_t bytes_off;     // delta byte-array pages: offset of the (suffix) bytes in the value section (k_delta_lengths)
   int64_t n_chars;
   // bases within the column (first tile's bases)
   int64_t row_base, entry_base, value_base, char_base;
@@ -46,7 +51,10 @@ struct DPage {
   // string positions (BYTE_ARRAY PLAIN data pages and dictionary pages): 16 KiB chunks (input)
   int32_t pchunk0, npchunk;
   int32_t pos_fail;      // speculative positions rejected -> serial walk (k_pos_fallback)
-  int32_t pad3;
+  // DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY data pages: the page's slots in the length scratch, in
+  // units of 4 int32 (input; per page 3 * (num_values + 1) int32: suffix lengths, prefix lengths,
+  // suffix offsets)
+  int32_t aux16;
 };
 
 // Speculative snappy decode (k_snap_*): compressed streams are cut into DK_SNAP_SEG-byte segments,

@@ -56,6 +56,10 @@ void launch_tile_chars(const DChunk*, DPage*, const uint8_t*, const int32_t*, co
 void launch_tile_scan2(DColumn*, int, DPage*, DTile*, DState*, hipStream_t);
 void launch_tile_decode(const DChunk*, DPage*, const DColumn*, const uint8_t*, const int32_t*, const long long*, const Seg*, const DTile*, int, int, DState*, hipStream_t);
 void launch_delta_decode(const DChunk*, DPage*, int, const uint8_t*, long long*, hipStream_t);
+void launch_delta_lengths(const DChunk*, DPage*, int, const uint8_t*, int32_t*, int32_t*, hipStream_t);
+void launch_bss_gather(const DChunk*, DPage*, int, const uint8_t*, long long*, hipStream_t);
+void launch_delta_copy(int, const DChunk*, const DPage*, int, int, int, const DColumn*, const uint8_t*, const int32_t*,
+                       const int32_t*, const int2*, int, hipStream_t);
 void launch_string_copy(const DChunk*, const DPage*, int, const DColumn*, const uint8_t*, const int32_t*, const int2*, hipStream_t,
                         int, int);
 void launch_json_canon(DJsonAction*, int, const uint8_t*, uint8_t*, uint32_t, DState*, hipStream_t);
@@ -1036,12 +1040,13 @@ static int phys_width(int phys, int tl) {
 // kernel timing (HIP events on the engine stream)
 // ------------------------------------------------------------------------------------------------
 struct KTimer {
-  static constexpr int K = 24;
-  const char* names[K] = {"k_page_headers", "unused", "k_tile_count", "k_tile_scan",
+  static constexpr int K = 29;
+  const char* names[K] = {"k_page_headers", "k_delta_lengths", "k_tile_count", "k_tile_scan",
                           "k_string_positions", "k_tile_decode", "k_string_copy", "k_json_canon",
                           "k_table_insert", "k_table_update", "k_json_select", "k_probe", "step_total",
                           "k_snap_walk_link", "k_delta_decode", "k_page_runs", "k_tile_chars", "k_stats_eval", "k_part_eval",
-                          "k_snap_fix", "k_snap_frag", "k_snappy_serial", "k_owner_route", "k_owner_resolve"};
+                          "k_snap_fix", "k_snap_frag", "k_snappy_serial", "k_owner_route", "k_owner_resolve",
+                          "k_bss_gather", "k_dlba_copy", "k_dba_tail", "k_dba_link", "k_dba_expand"};
   double sum_ms[K] = {0};
   int64_t cnt[K] = {0};
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
@@ -1162,6 +1167,10 @@ struct dk_parquet {
   std::vector<HBuf> staging;        // pinned sources of zero-copy uploads, released when prepare ends
   int n_pages = 0, n_cols = 0;
   bool has_compressed = false, has_dbp = false;
+  // DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY data pages (their length scratch: d_aux) and
+  // BYTE_STREAM_SPLIT pages (their values go through the DBP scratch)
+  bool has_dlba = false, has_dba = false, has_bss = false;
+  DBuf d_aux;
   int64_t bytes_read = 0, bytes_written = 0, bytes_arena = 0;
   KTimer timer;
   // host read + H2D issue, page metadata, prepare passes; inside prepare: H2D wait + headers,
@@ -1284,7 +1293,12 @@ static void sizing_stages(dk_parquet* p, hipStream_t s, const PRange& R) {
   { KTimer::Scope sc(&T, 3, s); launch_tile_scan1(cols + R.col0, R.col1 - R.col0, P, LT, st, s); }
   { KTimer::Scope sc(&T, 4, s); launch_positions(C, P, R.pa, np, arena, pos, p->d_pchunks.as<DPosChunk>(), R.pc0, R.pc1 - R.pc0,
                                                     p->d_pos_scratch.as<int16_t>(), s); }
+  if (p->has_dlba || p->has_dba) {
+    KTimer::Scope sc(&T, 1, s);
+    launch_delta_lengths(C, P + R.pa, np, arena, pos, p->d_aux.as<int32_t>(), s);
+  }
   if (p->has_dbp) { KTimer::Scope sc(&T, 14, s); launch_delta_decode(C, P + R.pa, np, arena, p->d_dbp.as<long long>(), s); }
+  if (p->has_bss) { KTimer::Scope sc(&T, 24, s); launch_bss_gather(C, P + R.pa, np, arena, p->d_dbp.as<long long>(), s); }
   { KTimer::Scope sc(&T, 16, s); launch_tile_chars(C, P, arena, pos, runs, LT, R.t1 - R.t0, R.t0, s); }
   { KTimer::Scope sc(&T, 3, s); launch_tile_scan2(cols + R.col0, R.col1 - R.col0, P, LT, st, s); }
 }
@@ -1308,6 +1322,17 @@ static void decode_cols(dk_parquet* p, hipStream_t s, int c0, int c1) {
     const int2* tiles = p->d_tiles.as<int2>();
     const int t0 = p->col_tile0[c0], t1 = p->col_tile0[c1];
     if (t1 > t0) launch_string_copy(C, P, t1 - t0, cols, arena, pos, tiles, s, t0, p->copy_cb);
+  }
+  if (p->has_dlba || p->has_dba) {                 // the delta byte-array pages among the same tiles
+    const int2* tiles = p->d_tiles.as<int2>();
+    const int32_t* aux = p->d_aux.as<int32_t>();
+    const int t0 = p->col_tile0[c0], nt = p->col_tile0[c1] - t0;
+    const int pa = p->h_cols[c0].first_page;
+    const int pb = p->h_cols[c1 - 1].first_page + p->h_cols[c1 - 1].n_pages;
+    for (int step = p->has_dlba ? 0 : 1; step < (p->has_dba ? 4 : 1); step++) {
+      KTimer::Scope sc(&T, 25 + step, s);
+      launch_delta_copy(step, C, P, pa, pb - pa, nt, cols, arena, pos, aux, tiles, t0, s);
+    }
   }
   {
     KTimer::Scope sc(&T, 5, s);
@@ -1423,7 +1448,10 @@ static void build_tiles(dk_parquet* p, int c0, int c1, std::vector<int2>& tiles)
     const DColumn& c = p->h_cols[ci];
     for (int pi = c.first_page; pi < c.first_page + c.n_pages; pi++) {
       const DPage& pg = p->h_pages[pi];
-      if (c.phys != PT_BYTE_ARRAY || (pg.flags & PF_DICT) || pg.enc != ENC_PLAIN) continue;
+      // (delta byte-array pages: the same tiles, taken by k_dlba_copy / k_dba_*)
+      if (c.phys != PT_BYTE_ARRAY || (pg.flags & PF_DICT) ||
+          (pg.enc != ENC_PLAIN && pg.enc != ENC_DELTA_LBA && pg.enc != ENC_DELTA_BA))
+        continue;
       for (int v0 = 0; v0 < pg.n_values; v0 += DK_COPY_TILE) tiles.push_back(make_int2(pi, v0));
     }
     // key column: its dictionary pages are hashed entry by entry (hash-only tiles)
@@ -1633,7 +1661,7 @@ static int prepare(dk_parquet* p) {
       return fail("Error reading Parquet file: " + f.path + " (bad page header at offset " +
                   std::to_string(file_offset(f, pg.hdr_off)) + ")");
   }
-  int64_t posn = 0, arena_n = 0, dbp_n = 0;
+  int64_t posn = 0, arena_n = 0, dbp_n = 0, aux_n = 0;
   // per-page work lists (fragments, segments, level tiles, position chunks) are expanded on the device
   // from per-group counts (k_expand): the host only builds the prefix arrays (one entry per page)
   std::vector<int32_t> cpage, fbase(1, 0), sbase(1, 0);
@@ -1641,6 +1669,7 @@ static int prepare(dk_parquet* p) {
     DPage& pg = p->h_pages[i];
     DChunk& ck = p->h_chunks[pg.chunk];
     pg.unc_off = -1;
+    pg.flags &= PF_DICT;                     // PF_POS / PF_SLOT64: set below
     if (ck.codec != CODEC_NONE) {
       if (ck.codec != CODEC_SNAPPY)
         return fail("Error reading Parquet file: " + p->files[p->col_file[ck.col]].path +
@@ -1664,15 +1693,35 @@ static int prepare(dk_parquet* p) {
     }
     if ((ck.phys == PT_INT32 || ck.phys == PT_INT64) && !(pg.flags & PF_DICT) && pg.enc == ENC_DELTA_BP) {
       pg.pos_base = dbp_n;
+      pg.flags |= PF_SLOT64;
       dbp_n += (int64_t)pg.num_values + 1;
       p->has_dbp = true;
     }
+    // BYTE_STREAM_SPLIT floats / doubles are transposed into slots of the same scratch (k_bss_gather)
+    if ((ck.phys == PT_FLOAT || ck.phys == PT_DOUBLE) && !(pg.flags & PF_DICT) && pg.enc == ENC_BYTE_STREAM_SPLIT) {
+      pg.pos_base = dbp_n;
+      pg.flags |= PF_SLOT64;
+      dbp_n += (int64_t)pg.num_values + 1;
+      p->has_bss = true;
+    }
     if (ck.phys == PT_BYTE_ARRAY) {
       if (pg.flags & PF_DICT) { ck.dict_pos = posn; }
-      else pg.pos_base = posn;
+      else {
+        pg.pos_base = posn;
+        if (pg.enc == ENC_PLAIN || pg.enc == ENC_DELTA_LBA || pg.enc == ENC_DELTA_BA) pg.flags |= PF_POS;
+      }
       posn += (int64_t)pg.num_values + 1;
+      // delta byte-array data pages: suffix lengths, prefix lengths and suffix offsets (k_delta_lengths)
+      pg.aux16 = 0; pg.bytes_off = 0;
+      if (!(pg.flags & PF_DICT) && (pg.enc == ENC_DELTA_LBA || pg.enc == ENC_DELTA_BA)) {
+        pg.aux16 = (int32_t)(aux_n / 4);
+        aux_n += (3 * ((int64_t)std::max(pg.num_values, 0) + 1) + 3) & ~(int64_t)3;
+        if (aux_n / 4 > INT32_MAX) return fail("internal: delta byte-array length scratch too large");
+        (pg.enc == ENC_DELTA_BA ? p->has_dba : p->has_dlba) = true;
+      }
     }
   }
+  if (p->d_aux.alloc((size_t)(aux_n + 16) * 4)) return 1;
   // level tiles and run-table scratch (standard writers emit >= 8 values per hybrid run; a stream
   // with more than num_values / 4 + 64 runs is reported as unsupported)
   {
@@ -1795,7 +1844,8 @@ static int prepare(dk_parquet* p) {
         if (c.phys != PT_BYTE_ARRAY) continue;
         for (int pi = c.first_page; pi < c.first_page + c.n_pages; pi++) {
           const DPage& pg = p->h_pages[pi];
-          if (!(pg.flags & PF_DICT) && pg.enc == ENC_PLAIN) nt += (std::max(pg.num_values, 0) + DK_COPY_TILE - 1) / DK_COPY_TILE;
+          if (!(pg.flags & PF_DICT) && (pg.enc == ENC_PLAIN || pg.enc == ENC_DELTA_LBA || pg.enc == ENC_DELTA_BA))
+            nt += (std::max(pg.num_values, 0) + DK_COPY_TILE - 1) / DK_COPY_TILE;
         }
       }
       for (const DChunk& ck : p->h_chunks)
@@ -2896,8 +2946,38 @@ extern "C" int dk_parquet_kernel_traffic(dk_parquet* p, const char* kernel, int6
       const DPage& pg = p->h_pages[pi];
       const int64_t body = pg.unc_off >= 0 ? pg.usize : pg.csize;
       const bool plain_str = c.phys == PT_BYTE_ARRAY && pg.enc == ENC_PLAIN;
+      const bool dlba = c.phys == PT_BYTE_ARRAY && pg.enc == ENC_DELTA_LBA;
+      const bool dba = c.phys == PT_BYTE_ARRAY && pg.enc == ENC_DELTA_BA;
+      const bool bss = pg.enc == ENC_BYTE_STREAM_SPLIT && (c.phys == PT_FLOAT || c.phys == PT_DOUBLE);
+      const int64_t nblk = (pg.n_values + DK_COPY_TILE - 1) / DK_COPY_TILE;
+      // (bytes_off is k_delta_lengths' result: prepare copies the pages back after the sizing passes)
+      const int64_t mean_suf = (dba && pg.n_values > 0) ? (pg.vbytes - pg.bytes_off) / pg.n_values : 0;
       if (k == "k_string_copy") {
         if (plain_str) { rd += pg.vbytes; wr += pg.n_chars + (key ? 8ll * pg.n_values : 0); }
+      } else if (k == "k_delta_lengths") {
+        // the length streams (the value section up to the byte section); lengths written and re-read
+        // for the scan, then the positions and suffix offsets (and DELTA_BYTE_ARRAY's prefixes)
+        if (dlba || dba) {
+          const int64_t nl = (dba ? 2 : 1) * (int64_t)pg.n_values;
+          rd += pg.bytes_off + 4 * nl; wr += 4 * nl + 8ll * pg.n_values;
+        }
+      } else if (k == "k_bss_gather") {
+        if (bss) { rd += (int64_t)c.width * pg.n_values; wr += 8ll * pg.n_values; }
+      } else if (k == "k_dlba_copy") {
+        if (dlba) { rd += pg.n_chars + 4ll * pg.n_values; wr += pg.n_chars + (key ? 8ll * pg.n_values : 0); }
+      } else if (k == "k_dba_tail") {
+        // a lower bound: the block's prefixes, the two positions and the suffix offsets of its last
+        // value; that value's own suffix (the page's mean suffix length stands for it) read and
+        // written. What the last value takes from earlier suffixes of the block is data dependent
+        // and not counted.
+        if (dba) { rd += 4ll * pg.n_values + 16 * nblk + mean_suf * nblk; wr += mean_suf * nblk; }
+      } else if (k == "k_dba_link") {
+        // a lower bound: the prefixes (block minima) and two positions per block; the copied bytes
+        // (each block's minimum prefix, read and written) are data dependent and not counted
+        if (dba) { rd += 4ll * pg.n_values + 8 * nblk; }
+      } else if (k == "k_dba_expand") {
+        // prefixes, suffix offsets, positions; the suffix bytes in, every value's bytes out
+        if (dba) { rd += 12ll * pg.n_values + (pg.vbytes - pg.bytes_off); wr += pg.n_chars + (key ? 8ll * pg.n_values : 0); }
       } else if (k == "k_snap_frag") {
         // snappy pages: compressed body read, decompressed body written (v2 levels excluded)
         if (pg.unc_off >= 0) {
@@ -2906,13 +2986,15 @@ extern "C" int dk_parquet_kernel_traffic(dk_parquet* p, const char* kernel, int6
         }
       } else if (k == "k_tile_decode") {
         rd += body - pg.vbytes;                                   // level streams
-        if (!plain_str) rd += pg.vbytes;                          // values / dictionary indices
+        const bool pos_str = plain_str || dlba || dba;            // chars placed by a copy kernel
+        if (bss) rd += 8ll * pg.n_values;                         // k_bss_gather's slots
+        else if (!pos_str) rd += pg.vbytes;                       // values / dictionary indices
         else rd += 4ll * pg.n_values + (key ? 8ll * pg.n_values : 0);   // positions (+ value hashes)
         wr += pg.n_rows;                                          // row_def
         if (c.max_rep > 0) wr += 8ll * pg.n_rows + pg.n_entries;  // row_offs, entry_def
         if (!c.null_only) {
           const int64_t nv = c.max_rep > 0 ? pg.n_entries : pg.n_rows;
-          if (c.phys == PT_BYTE_ARRAY) wr += 8ll * nv + (plain_str ? 0 : pg.n_chars);   // offs (+ dict chars)
+          if (c.phys == PT_BYTE_ARRAY) wr += 8ll * nv + (pos_str ? 0 : pg.n_chars);   // offs (+ dict chars)
           else wr += (int64_t)c.width * nv;
         }
         if (key) wr += 8ll * pg.n_rows;                           // key hash per row
@@ -5816,7 +5898,7 @@ extern "C" int dk_replay_stats_parsed_files(dk_replay* r) {
 extern "C" int dk_replay_kernel_stats(dk_replay* r, int32_t i, const char** name, double* avg_us, int64_t* count) {
   if (i < 0 || i >= KTimer::K) return 1;
   // decode kernels are timed by the parquet object's timer, the rest by the replay's
-  const KTimer* t = (r->ck && (i <= 6 || (i >= 13 && i <= 16) || (i >= 19 && i <= 21))) ? &r->ck->timer : &r->timer;
+  const KTimer* t = (r->ck && (i <= 6 || (i >= 13 && i <= 16) || (i >= 19 && i <= 21) || i >= 24)) ? &r->ck->timer : &r->timer;
   *name = t->names[i];
   if (!*name) return 1;
   *count = t->cnt[i];

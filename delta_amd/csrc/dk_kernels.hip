@@ -11,6 +11,9 @@
 //                       candidates + exact chain verification, sequential fallback
 //   k_tile_count / k_tile_scan1 / k_tile_chars / k_tile_scan2   rows, entries, values, chars
 //   k_delta_decode      DELTA_BINARY_PACKED
+//   k_delta_lengths     DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY length streams -> offsets, positions
+//   k_bss_gather        BYTE_STREAM_SPLIT floats / doubles -> the DBP scratch
+//   k_dlba_copy, k_dba_tail / k_dba_link / k_dba_expand   their bytes -> contiguous chars + key-path hashes
 //   k_string_copy       PLAIN string bytes -> contiguous chars + key-path hashes
 //   k_tile_decode       levels + values -> row_def / row_offs / entry_def / fixed / offs
 //   k_json_canon / k_table_insert / k_table_update / k_json_select   commit-tail keys
@@ -1700,7 +1703,8 @@ struct DbpLds {
   long long block_min;
   int mini_in_block, blk_left;         // next miniblock index in the current block
   const uint8_t* bws;
-  const uint8_t* data;
+  const uint8_t* data;                 // after the walk: the first byte behind the stream
+  uint64_t hblock, hnmini, htotal;     // stream header
 };
 
 __device__ __forceinline__ uint64_t uvarint(const uint8_t*& p, const uint8_t* e, int* err) {
@@ -1715,37 +1719,37 @@ __device__ __forceinline__ uint64_t uvarint(const uint8_t*& p, const uint8_t* e,
   return 0;
 }
 
-__global__ __launch_bounds__(NT) void k_delta_decode(const DChunk* __restrict__ chunks, DPage* __restrict__ pages,
-                                                     const uint8_t* __restrict__ arena, long long* __restrict__ dbp) {
-  DPage& pgw = pages[blockIdx.x];
-  const DPage pg = pgw;                            // by value: stores below may alias
-  if ((pg.flags & PF_DICT) || pg.status != PS_OK || pg.enc != ENC_DELTA_BP) return;
-  const DChunk ck = chunks[pg.chunk];
-  if (ck.phys != PT_INT32 && ck.phys != PT_INT64) return;
-  Layout L = page_layout(pg, ck, arena);
+// The walk of one DELTA_BINARY_PACKED stream by a whole workgroup: the stream starts at p0 (anywhere
+// in the value section, which ends at val_e), its first n values go to sink(i, value), and S.data is
+// left on the first byte behind the stream -- known only after the last miniblock, which is how the
+// byte-array encodings find their next section. The last block follows the format's rule: the
+// bit-width bytes of its unneeded miniblocks are present and never read as widths, their data is
+// absent, the last needed miniblock is whole. exact: the header must count n values and every
+// miniblock must lie inside the value section (a stream that locates what follows it); otherwise
+// n values of a longer stream are taken, as the integer columns always were. S.err != 0: malformed.
+template <class Sink>
+__device__ __forceinline__ void dbp_walk(DbpLds& S, const uint8_t* val_p, const uint8_t* p0, const uint8_t* val_e,
+                                         const int n, const bool exact, Sink sink) {
   const int t = threadIdx.x;
-  const int n = pg.n_values;
-  long long* out = dbp + pg.pos_base;
-  __shared__ DbpLds S;
-  __shared__ uint64_t s_block, s_nmini, s_total;
+  struct { const uint8_t* val_p; const uint8_t* val_e; } L = {val_p, val_e};
   if (t == 0) {
     int err = 0;
-    const uint8_t* p = L.val_p;
-    s_block = uvarint(p, L.val_e, &err);
-    s_nmini = uvarint(p, L.val_e, &err);
-    s_total = uvarint(p, L.val_e, &err);
+    const uint8_t* p = p0;
+    S.hblock = uvarint(p, L.val_e, &err);
+    S.hnmini = uvarint(p, L.val_e, &err);
+    S.htotal = uvarint(p, L.val_e, &err);
     uint64_t z = uvarint(p, L.val_e, &err);
     long long first = (long long)(z >> 1) ^ -(long long)(z & 1);
-    if (s_nmini == 0 || s_block % s_nmini || (s_block / s_nmini) % 32 || (long long)s_total < n ||
-        s_nmini > DBP_MAXMINI)
+    if (S.hnmini == 0 || S.hblock % S.hnmini || (S.hblock / S.hnmini) % 32 || (long long)S.htotal < n ||
+        S.hnmini > DBP_MAXMINI || (exact && (long long)S.htotal != n))
       err = 1;
-    S.p = p; S.carry = first; S.err = err; S.blk_left = 0; S.mini_in_block = 0;
-    if (n > 0 && !err) out[0] = ck.phys == PT_INT32 ? (long long)(int32_t)first : first;
+    S.p = p; S.data = p; S.carry = first; S.err = err; S.blk_left = 0; S.mini_in_block = 0;
+    if (n > 0 && !err) sink(0, first);
   }
   __syncthreads();
-  if (S.err) { if (t == 0) pgw.status = PS_BAD_VALUES; return; }
-  const int per_mini = (int)(s_block / s_nmini);
-  const int nmini_blk = (int)s_nmini;
+  if (S.err) return;
+  const int per_mini = (int)(S.hblock / S.hnmini);
+  const int nmini_blk = (int)S.hnmini;
   const long long ndelta = n > 0 ? n - 1 : 0;
   for (long long d0 = 0; d0 < ndelta;) {
     if (t == 0) {
@@ -1770,6 +1774,7 @@ __global__ __launch_bounds__(NT) void k_delta_decode(const DChunk* __restrict__ 
         S.mini_first[nm] = got;
         nm++;
         S.data += (long long)per_mini * bw / 8;
+        if (exact && (bw > 64 || S.data > L.val_e)) { err = 1; break; }
         S.mini_in_block++;
         if (S.mini_in_block == nmini_blk) S.p = S.data;
         got += per_mini;
@@ -1816,7 +1821,7 @@ __global__ __launch_bounds__(NT) void k_delta_decode(const DChunk* __restrict__ 
       int i = t * 4 + k;
       if (i < win) {
         run = (long long)((uint64_t)run + (uint64_t)dv[k]);
-        out[d0 + i + 1] = ck.phys == PT_INT32 ? (long long)(int32_t)run : run;
+        sink((int)(d0 + i + 1), run);
       }
     }
     __syncthreads();
@@ -1824,7 +1829,146 @@ __global__ __launch_bounds__(NT) void k_delta_decode(const DChunk* __restrict__ 
     d0 += win;
     __syncthreads();
   }
-  if (S.err && t == 0) pgw.status = PS_BAD_VALUES;
+}
+
+__global__ __launch_bounds__(NT) void k_delta_decode(const DChunk* __restrict__ chunks, DPage* __restrict__ pages,
+                                                     const uint8_t* __restrict__ arena, long long* __restrict__ dbp) {
+  DPage& pgw = pages[blockIdx.x];
+  const DPage pg = pgw;                            // by value: stores below may alias
+  if ((pg.flags & PF_DICT) || pg.status != PS_OK || pg.enc != ENC_DELTA_BP) return;
+  const DChunk ck = chunks[pg.chunk];
+  if (ck.phys != PT_INT32 && ck.phys != PT_INT64) return;
+  const Layout L = page_layout(pg, ck, arena);
+  long long* out = dbp + pg.pos_base;
+  const bool i32 = ck.phys == PT_INT32;
+  __shared__ DbpLds S;
+  dbp_walk(S, L.val_p, L.val_p, L.val_e, pg.n_values, false,
+           [&](int i, long long v) { out[i] = i32 ? (long long)(int32_t)v : v; });
+  if (S.err && threadIdx.x == 0) pgw.status = PS_BAD_VALUES;
+}
+
+// --------------------------------------------------------------------------------------------
+// K2c: the length streams of DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY pages, one workgroup per
+// page. DELTA_LENGTH_BYTE_ARRAY is one DBP stream of n lengths and then the values' bytes, back to
+// back; DELTA_BYTE_ARRAY is a DBP stream of n prefix lengths and then the suffixes as a
+// DELTA_LENGTH_BYTE_ARRAY stream, value i = value[i-1][0:prefix[i]] + suffix[i], the chain
+// restarting on every page. The kernel walks the streams (dbp_walk), checks every length
+// (0 <= length, prefix[0] == 0, prefix[i] <= length of value i-1, the suffix bytes inside the page
+// body) and scans them:
+//   aux SO[0..n]   offsets of the (suffix) bytes in the byte section, which starts bytes_off behind
+//                  the value section's start
+//   aux PR[0..n)   prefix lengths (DELTA_LENGTH_BYTE_ARRAY: none)
+//   pos P[0..n]    the page's position slots: output offset of value i + 4 * i. That is what a PLAIN
+//                  page's positions are to its chars (offset of the 4-byte length prefix), so
+//                  k_tile_chars and k_tile_decode size and place these pages with PLAIN's arithmetic.
+// A page that fails a check gets PS_BAD_VALUES and none of its lengths is ever used as an address.
+// --------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool delta_ba_enc(int32_t enc) { return enc == ENC_DELTA_LBA || enc == ENC_DELTA_BA; }
+
+__global__ __launch_bounds__(NT) void k_delta_lengths(const DChunk* __restrict__ chunks, DPage* __restrict__ pages,
+                                                      const uint8_t* __restrict__ arena, int32_t* __restrict__ pos,
+                                                      int32_t* __restrict__ aux) {
+  DPage& pgw = pages[blockIdx.x];
+  const DPage pg = pgw;                            // by value: stores below may alias
+  if ((pg.flags & PF_DICT) || pg.status != PS_OK || !delta_ba_enc(pg.enc)) return;
+  const DChunk ck = chunks[pg.chunk];
+  if (ck.phys != PT_BYTE_ARRAY) return;
+  const Layout L = page_layout(pg, ck, arena);
+  if (!L.ok) return;
+  const int t = threadIdx.x;
+  const int n = pg.n_values;
+  const int slots = (pg.num_values > 0 ? pg.num_values : 0) + 1;
+  int32_t* P = pos + pg.pos_base;
+  int32_t* SL = aux + 4 * (int64_t)pg.aux16;      // suffix lengths
+  int32_t* PR = SL + slots;
+  int32_t* SO = PR + slots;
+  if (n <= 0 || n >= slots) {                      // no value: nothing to walk (the body may be empty)
+    if (t == 0) { P[0] = 0; SO[0] = 0; pgw.bytes_off = 0; if (n > 0) pgw.status = PS_BAD_VALUES; }
+    return;
+  }
+  const bool ba = pg.enc == ENC_DELTA_BA;
+  __shared__ DbpLds S;
+  __shared__ long long l64[4];
+  __shared__ int s_bad;
+  if (t == 0) s_bad = 0;
+  __syncthreads();
+  auto len_sink = [&](int32_t* dst) {
+    return [dst](int i, long long v) {
+      dst[i] = (v < 0 || v > 0x7fffffffll) ? -1 : (int32_t)v;
+    };
+  };
+  const uint8_t* p = L.val_p;
+  if (ba) {
+    dbp_walk(S, L.val_p, p, L.val_e, n, true, len_sink(PR));
+    __syncthreads();
+    if (S.err) { if (t == 0) pgw.status = PS_BAD_VALUES; return; }
+    p = S.data;
+    __syncthreads();
+  }
+  dbp_walk(S, L.val_p, p, L.val_e, n, true, len_sink(SL));
+  __syncthreads();                                 // the lengths are in memory for the whole workgroup
+  if (S.err) { if (t == 0) pgw.status = PS_BAD_VALUES; return; }
+  const uint8_t* bytes = S.data;
+  const long long room = (long long)(L.val_e - bytes);
+  long long run_s = 0, run_o = 0;
+  bool bad = room < 0;
+  for (int i0 = 0; i0 < n; i0 += NT) {
+    const int i = i0 + t;
+    long long sl = 0, pl = 0;
+    if (i < n) {
+      sl = SL[i];
+      pl = ba ? PR[i] : 0;
+      if (sl < 0 || pl < 0) { bad = true; sl = 0; pl = 0; }
+      // the prefix is taken from the previous value: none before the page's first value
+      if (ba && pl > (i == 0 ? 0ll : (long long)PR[i - 1] + (long long)SL[i - 1])) bad = true;
+    }
+    long long ts, to;
+    const long long es = block_scan64(sl, &ts, l64);
+    const long long eo = block_scan64(sl + pl, &to, l64);
+    if (i < n) {
+      SO[i] = (int32_t)(run_s + es);
+      P[i] = (int32_t)(run_o + eo + 4ll * i);
+    }
+    run_s += ts; run_o += to;
+  }
+  if (run_s > room || run_o + 4ll * n > 0x7fffffffll) bad = true;
+  if (bad) s_bad = 1;
+  __syncthreads();
+  if (t == 0) {
+    SO[n] = (int32_t)run_s;
+    P[n] = (int32_t)(run_o + 4ll * n);
+    pgw.bytes_off = (int32_t)(bytes - L.val_p);
+    if (s_bad) pgw.status = PS_BAD_VALUES;
+  }
+}
+
+// BYTE_STREAM_SPLIT (FLOAT, DOUBLE): byte k of the page's non-null value i of n lies at body[k * n + i].
+// Consecutive lanes take consecutive values, so each of the width loads reads consecutive bytes
+// across the wave and the 8-byte store to the page's slots of the DBP scratch is coalesced;
+// k_tile_decode places the values from there as it places DELTA_BINARY_PACKED ones.
+constexpr int BSS_Y = 8;               // workgroups per page
+__global__ __launch_bounds__(NT) void k_bss_gather(const DChunk* __restrict__ chunks, DPage* __restrict__ pages,
+                                                   const uint8_t* __restrict__ arena, long long* __restrict__ dbp) {
+  DPage& pgw = pages[blockIdx.x];
+  const DPage pg = pgw;
+  if ((pg.flags & PF_DICT) || pg.status != PS_OK || pg.enc != ENC_BYTE_STREAM_SPLIT) return;
+  const DChunk ck = chunks[pg.chunk];
+  if (ck.phys != PT_FLOAT && ck.phys != PT_DOUBLE) return;
+  const Layout L = page_layout(pg, ck, arena);
+  if (!L.ok) return;
+  const int n = pg.n_values;
+  const int w = ck.width;
+  if (n <= 0) return;
+  if (n > pg.num_values || (long long)n * w > (long long)(L.val_e - L.val_p)) {
+    if (threadIdx.x == 0 && blockIdx.y == 0) pgw.status = PS_BAD_VALUES;
+    return;
+  }
+  long long* out = dbp + pg.pos_base;
+  for (int i = (int)blockIdx.y * NT + (int)threadIdx.x; i < n; i += BSS_Y * NT) {
+    uint64_t x = 0;
+    for (int k = 0; k < w; k++) x |= (uint64_t)L.val_p[(int64_t)k * n + i] << (8 * k);
+    out[i] = (long long)x;
+  }
 }
 
 // --------------------------------------------------------------------------------------------
@@ -1941,9 +2085,11 @@ __global__ void k_page_runs(const DChunk* __restrict__ chunks, DPage* __restrict
 // encodings the value decoder supports for this page (values present)
 __device__ __forceinline__ bool enc_supported(const DPage& pg, const DChunk& ck) {
   const bool dict = (pg.enc == ENC_PLAIN_DICT || pg.enc == ENC_RLE_DICT) && ck.dict_page >= 0;
-  if (ck.phys == PT_BYTE_ARRAY) return pg.enc == ENC_PLAIN || dict;
+  // DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY: BYTE_ARRAY only (not FIXED_LEN_BYTE_ARRAY)
+  if (ck.phys == PT_BYTE_ARRAY) return pg.enc == ENC_PLAIN || dict || delta_ba_enc(pg.enc);
   return pg.enc == ENC_PLAIN || dict || (pg.enc == ENC_RLE && ck.phys == PT_BOOLEAN) ||
-         (pg.enc == ENC_DELTA_BP && (ck.phys == PT_INT32 || ck.phys == PT_INT64));
+         (pg.enc == ENC_DELTA_BP && (ck.phys == PT_INT32 || ck.phys == PT_INT64)) ||
+         (pg.enc == ENC_BYTE_STREAM_SPLIT && (ck.phys == PT_FLOAT || ck.phys == PT_DOUBLE));
 }
 
 __global__ __launch_bounds__(NT) void k_tile_count(const DChunk* __restrict__ chunks, DPage* __restrict__ pages,
@@ -2032,7 +2178,7 @@ __global__ __launch_bounds__(NT) void k_tile_chars(const DChunk* __restrict__ ch
   const int nvt = T.n_values;
   const int vb = (int)(T.value_base - pg.value_base);     // page-local index of the tile's first value
   if (pg.status != PS_OK || nvt == 0) { if (t == 0) T.n_chars = 0; return; }
-  if (pg.enc == ENC_PLAIN) {
+  if (pg.enc == ENC_PLAIN || delta_ba_enc(pg.enc)) {   // (the delta encodings' slots: k_delta_lengths)
     if (t == 0) {
       const int32_t* P = pos + pg.pos_base;
       T.n_chars = (long long)(P[vb + nvt] - P[vb]) - 4ll * nvt;
@@ -2164,7 +2310,7 @@ __global__ __launch_bounds__(NT) void k_tile_decode(const DChunk* __restrict__ c
     if (is_str) DP = pos + ck.dict_pos;
     ibw = L.val_p < L.val_e ? (int)(*L.val_p) : 0;
   }
-  const int32_t* P = (is_str && pg.enc == ENC_PLAIN) ? pos + pg.pos_base : nullptr;
+  const int32_t* P = (is_str && (pg.flags & PF_POS)) ? pos + pg.pos_base : nullptr;
   __shared__ int s_fill;
   // null-only column whose def levels over the whole tile are ONE RLE run: every level is a row
   // with the same def level and nothing but row_def is materialised -> a vectorised fill. A repeated
@@ -2325,7 +2471,7 @@ __global__ __launch_bounds__(NT) void k_tile_decode(const DChunk* __restrict__ c
         if (w == 8) *(uint64_t*)o = 0; else if (w == 4) *(uint32_t*)o = 0; else for (int j = 0; j < w; j++) o[j] = 0;
       } else if (ck.phys == PT_BOOLEAN) {
         *o = bool_rle ? (uint8_t)ix[k] : (uint8_t)((L.val_p[vloc >> 3] >> (vloc & 7)) & 1);
-      } else if (pg.enc == ENC_DELTA_BP) {
+      } else if (pg.flags & PF_SLOT64) {                   // DELTA_BINARY_PACKED, BYTE_STREAM_SPLIT
         const long long x = dbp[pg.pos_base + vloc];
         if (w == 8) *(long long*)o = x; else *(int32_t*)o = (int32_t)x;
       } else {
@@ -2563,6 +2709,233 @@ __device__ int simple_key_equal(const uint8_t* p, int32_t pl, const uint8_t* key
     if (eq) eq = (load8_any(key + 1, j) & mask) == a;
   }
   return eq ? 1 : 0;
+}
+
+// --------------------------------------------------------------------------------------------
+// K6b: the bytes of DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY pages -> contiguous output chars and
+// key-path hashes. The workgroups are the string-copy tiles of those pages (DK_COPY_TILE values of
+// one page each, k_string_copy leaves them alone); SO / PR / P are k_delta_lengths' results, all
+// checked there, so every offset below lies inside the page body and the column's chars.
+//
+// DELTA_LENGTH_BYTE_ARRAY (k_dlba_copy): the byte section already is the page's chars: a dense copy,
+// one aligned dwordx4 store per lane from a funnel-shifted source.
+//
+// DELTA_BYTE_ARRAY: "keep p bytes of the previous value, append s" composes -- (p1, s1) then (p2, s2)
+// keeps min(p1, p2) bytes -- so a page is reconstructed block-parallel, a block being one tile:
+//   k_dba_tail    every block: its minimum prefix m and the bytes of its last value from m on, each
+//                 byte found by a walk back over the block's prefixes in LDS (the nearest value whose
+//                 prefix does not cover it supplied it), written to the value's place in chars;
+//   k_dba_link    one workgroup per page runs over the blocks in order: the first m bytes of a
+//                 block's last value are those of the previous block's last value (complete by
+//                 then). The only serial part: one short copy per block;
+//   k_dba_expand  every block: starting from the previous block's last value it steps through its
+//                 values with the current value's first DBA_CUR bytes in LDS (the block's suffix
+//                 bytes staged in LDS too when they fit), each step byte-parallel across the lanes;
+//                 bytes past DBA_CUR are resolved by the walk back (through HBM: slow, correct).
+// Key column: every value's path hash over the produced bytes (0 = not simple, the probe recomputes).
+// --------------------------------------------------------------------------------------------
+constexpr int DBA_CUR = 2048;          // bytes of the current value kept in LDS
+constexpr int DBA_SUF = 6144;          // suffix bytes of a block staged in LDS
+
+struct DeltaTile {
+  const int32_t* P; const int32_t* SO; const int32_t* PR;
+  const uint8_t* bytes;                // the (suffix) byte section
+  uint8_t* chars;                      // the page's chars in the column (null: not materialised)
+  uint64_t* vh;                        // the page's value hashes (null: not a key column)
+  int v0, n;                           // values [v0, n) of the page
+};
+// output offset of value v within the page's chars
+__device__ __forceinline__ int32_t dt_out(const DeltaTile& D, int v) { return D.P[v] - 4 * v; }
+
+__device__ __forceinline__ bool delta_tile(const DChunk* chunks, const DPage* pages, const DColumn* cols,
+                                           const uint8_t* arena, const int32_t* pos, const int32_t* aux, int2 tile,
+                                           int32_t enc, DeltaTile& D) {
+  const DPage& pg = pages[tile.x];
+  if (pg.status != PS_OK || (pg.flags & PF_DICT) || pg.enc != enc) return false;
+  const DChunk& ck = chunks[pg.chunk];
+  if (ck.phys != PT_BYTE_ARRAY) return false;
+  const DColumn& col = cols[ck.col];
+  if (col.null_only) return false;
+  const int slots = (pg.num_values > 0 ? pg.num_values : 0) + 1;
+  D.P = pos + pg.pos_base;
+  D.PR = aux + 4 * (int64_t)pg.aux16 + slots;
+  D.SO = D.PR + slots;
+  D.bytes = page_layout(pg, ck, arena).val_p + pg.bytes_off;
+  D.chars = (col.chars && pg.n_chars > 0) ? col.chars + pg.char_base : nullptr;
+  D.vh = col.vhash ? col.vhash + pg.value_base : nullptr;
+  D.v0 = tile.y;
+  D.n = min(pg.n_values, tile.y + CT);
+  return D.n > D.v0 && (D.chars || D.vh);
+}
+
+__device__ __forceinline__ uint64_t delta_value_hash(const uint8_t* p, int32_t len) {
+  auto load8 = [&](int32_t j) -> uint64_t { return load8_any(p, j); };
+  uint64_t h = 0;
+  if (!simple_path_hash(len, load8, kDecodeSeed, &h)) h = 0;
+  return h;
+}
+
+__global__ __launch_bounds__(CT) void k_dlba_copy(const DChunk* __restrict__ chunks, const DPage* __restrict__ pages,
+                                                  const DColumn* __restrict__ cols, const uint8_t* __restrict__ arena,
+                                                  const int32_t* __restrict__ pos, const int32_t* __restrict__ aux,
+                                                  const int2* __restrict__ tiles, int tile0) {
+  DeltaTile D;
+  if (!delta_tile(chunks, pages, cols, arena, pos, aux, tiles[tile0 + blockIdx.x], ENC_DELTA_LBA, D)) return;
+  const int t = threadIdx.x;
+  const int32_t a0 = D.SO[D.v0], a1 = D.SO[D.n];
+  if (D.chars && a1 > a0) {
+    const uint8_t* src = D.bytes + a0;
+    const uintptr_t d0 = (uintptr_t)(D.chars + a0), d1 = d0 + (uintptr_t)(a1 - a0);
+    for (uintptr_t c = (d0 & ~(uintptr_t)15) + (uintptr_t)t * 16; c < d1; c += (uintptr_t)CT * 16) {
+      if (c >= d0 && c + 16 <= d1) {
+        const uintptr_t sa = (uintptr_t)src + (c - d0);
+        const uint32_t* q = (const uint32_t*)(sa & ~(uintptr_t)3);
+        const uint32_t sh = (uint32_t)(sa & 3);
+        const uint32_t w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3], w4 = sh ? q[4] : 0u;
+        *(uint4*)c = make_uint4(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
+                                __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh));
+      } else {                                     // an edge chunk, shared with the neighbouring tile
+        const uintptr_t lo = c > d0 ? c : d0, hi = c + 16 < d1 ? c + 16 : d1;
+        for (uintptr_t x = lo; x < hi; x++) *(uint8_t*)x = src[x - d0];
+      }
+    }
+  }
+  const int v = D.v0 + t;
+  if (D.vh && v < D.n) D.vh[v] = delta_value_hash(D.bytes + D.SO[v], D.SO[v + 1] - D.SO[v]);
+}
+
+// the byte j of value i (block-local index, spre = the block's prefixes) when a suffix of the block
+// supplied it: the nearest value k <= i whose prefix does not cover j. False: it is a byte of the
+// value before the block.
+__device__ __forceinline__ bool dba_walk_back(const DeltaTile& D, const int32_t* spre, int i, int32_t j, uint8_t* out) {
+  int k = i;
+  while (k >= 0 && spre[k] > j) k--;
+  if (k < 0) return false;
+  const int32_t o = j - spre[k], a = D.SO[D.v0 + k];
+  *out = (o < D.SO[D.v0 + k + 1] - a) ? D.bytes[a + o] : (uint8_t)0;   // (always inside: k_delta_lengths' checks)
+  return true;
+}
+
+__global__ __launch_bounds__(CT) void k_dba_tail(const DChunk* __restrict__ chunks, const DPage* __restrict__ pages,
+                                                 const DColumn* __restrict__ cols, const uint8_t* __restrict__ arena,
+                                                 const int32_t* __restrict__ pos, const int32_t* __restrict__ aux,
+                                                 const int2* __restrict__ tiles, int tile0) {
+  DeltaTile D;
+  if (!delta_tile(chunks, pages, cols, arena, pos, aux, tiles[tile0 + blockIdx.x], ENC_DELTA_BA, D) || !D.chars) return;
+  const int t = threadIdx.x;
+  __shared__ int32_t spre[CT];
+  __shared__ int32_t smin[CT / 64];
+  const int nb = D.n - D.v0;
+  int32_t m = t < nb ? D.PR[D.v0 + t] : 0x7fffffff;
+  spre[t] = m;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o, 64));
+  if ((t & 63) == 0) smin[t >> 6] = m;
+  __syncthreads();
+  m = smin[0];
+#pragma unroll
+  for (int q = 1; q < CT / 64; q++) m = min(m, smin[q]);
+  const int last = nb - 1;
+  const int32_t o0 = dt_out(D, D.n - 1), len = dt_out(D, D.n) - o0;
+  for (int32_t j = m + t; j < len; j += CT) {
+    uint8_t b = 0;
+    if (dba_walk_back(D, spre, last, j, &b)) D.chars[o0 + j] = b;
+  }
+}
+
+__global__ __launch_bounds__(NT) void k_dba_link(const DChunk* __restrict__ chunks, const DPage* __restrict__ pages,
+                                                 const DColumn* __restrict__ cols, const int32_t* __restrict__ pos,
+                                                 const int32_t* __restrict__ aux) {
+  const DPage& pg = pages[blockIdx.x];
+  if (pg.status != PS_OK || (pg.flags & PF_DICT) || pg.enc != ENC_DELTA_BA) return;
+  const DChunk& ck = chunks[pg.chunk];
+  if (ck.phys != PT_BYTE_ARRAY) return;
+  const DColumn& col = cols[ck.col];
+  const int n = pg.n_values;
+  if (col.null_only || !col.chars || pg.n_chars <= 0 || n <= CT) return;
+  constexpr int LB = 1024;                         // blocks per pass: their minimum prefixes in LDS
+  constexpr int NW = NT / 64;
+  __shared__ int32_t smin[LB];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int slots = (pg.num_values > 0 ? pg.num_values : 0) + 1;
+  const int32_t* P = pos + pg.pos_base;
+  const int32_t* PR = aux + 4 * (int64_t)pg.aux16 + slots;
+  uint8_t* chars = col.chars + pg.char_base;
+  const int nblk = (n + CT - 1) / CT;
+  for (int c0 = 0; c0 < nblk; c0 += LB) {
+    const int c1 = min(c0 + LB, nblk);
+    for (int b = c0 + wv; b < c1; b += NW) {       // one wave per block: its minimum prefix
+      int32_t m = 0x7fffffff;
+      for (int v = b * CT + lane; v < min(b * CT + CT, n); v += 64) m = min(m, PR[v]);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o, 64));
+      if (lane == 0) smin[b - c0] = m;
+    }
+    __syncthreads();
+    for (int b = max(c0, 1); b < c1; b++) {
+      const int32_t m = smin[b - c0];              // uniform: the barrier below is taken by all or none
+      if (m <= 0) continue;
+      const int vs = b * CT - 1, vd = min(b * CT + CT, n) - 1;
+      const uint8_t* src = chars + (P[vs] - 4 * vs);
+      uint8_t* dst = chars + (P[vd] - 4 * vd);
+      for (int32_t j = t; j < m; j += NT) dst[j] = src[j];
+      __syncthreads();                             // the next block reads these bytes
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(CT) void k_dba_expand(const DChunk* __restrict__ chunks, const DPage* __restrict__ pages,
+                                                   const DColumn* __restrict__ cols, const uint8_t* __restrict__ arena,
+                                                   const int32_t* __restrict__ pos, const int32_t* __restrict__ aux,
+                                                   const int2* __restrict__ tiles, int tile0) {
+  DeltaTile D;
+  if (!delta_tile(chunks, pages, cols, arena, pos, aux, tiles[tile0 + blockIdx.x], ENC_DELTA_BA, D)) return;
+  const int t = threadIdx.x;
+  if (!D.chars) {                                  // a page of empty strings: only their hashes
+    if (D.v0 + t < D.n) D.vh[D.v0 + t] = delta_value_hash(nullptr, 0);
+    return;
+  }
+  __shared__ int32_t spre[CT], sout[CT + 1], ssuf[CT + 1];
+  __shared__ uint4 cur4[DBA_CUR / 16], suf4[DBA_SUF / 16 + 1];
+  uint8_t* cur = (uint8_t*)cur4;
+  const int nb = D.n - D.v0;
+  if (t < nb) { spre[t] = D.PR[D.v0 + t]; sout[t] = dt_out(D, D.v0 + t); ssuf[t] = D.SO[D.v0 + t]; }
+  if (t == 0) { sout[nb] = dt_out(D, D.n); ssuf[nb] = D.SO[D.n]; }
+  __syncthreads();
+  // the block's suffix bytes into LDS (aligned dwordx4 loads; sb = their misalignment)
+  const int32_t s0 = ssuf[0], sn = ssuf[nb] - s0;
+  const uintptr_t ga = (uintptr_t)(D.bytes + s0), gb = ga & ~(uintptr_t)15;
+  const int32_t sb = (int32_t)(ga - gb);
+  const bool staged = sb + sn <= DBA_SUF;
+  if (staged)
+    for (int q = t; q * 16 < sb + sn; q += CT) suf4[q] = ((const uint4*)gb)[q];
+  const uint8_t* suf8 = (const uint8_t*)suf4 + sb;
+  // the value before the block (complete: k_dba_link), as far as the block's first prefix reaches
+  const uint8_t* X = D.v0 > 0 ? D.chars + dt_out(D, D.v0 - 1) : nullptr;
+  for (int32_t j = t; j < min(spre[0], DBA_CUR); j += CT) cur[j] = X[j];
+  __syncthreads();
+  for (int i = 0; i + 1 < nb; i++) {               // (the block's last value: k_dba_tail / k_dba_link)
+    const int32_t pre = spre[i], len = sout[i + 1] - sout[i], so = ssuf[i] - s0;
+    uint8_t* out = D.chars + sout[i];
+    for (int32_t j = t; j < len; j += CT) {
+      uint8_t b;
+      if (j >= pre) {
+        b = staged ? suf8[so + (j - pre)] : D.bytes[s0 + so + (j - pre)];
+        if (j < DBA_CUR) cur[j] = b;
+      } else if (j < DBA_CUR) {
+        b = cur[j];
+      } else if (!dba_walk_back(D, spre, i - 1, j, &b)) {
+        b = X[j];
+      }
+      out[j] = b;
+    }
+    __syncthreads();
+  }
+  if (D.vh) {                                      // (the barriers above order this workgroup's stores)
+    const int v = D.v0 + t;
+    if (v < D.n) D.vh[v] = delta_value_hash(D.chars + sout[t], sout[t + 1] - sout[t]);
+  }
 }
 
 __device__ __forceinline__ void set_err(DState* st, int flag, long long row, int part) {
@@ -4704,6 +5077,26 @@ void launch_string_copy(const DChunk* c, const DPage* p, int ntiles, const DColu
     hipLaunchKernelGGL(k_string_copy, dim3(ntiles), dim3(CT), 2 * (cb + 32), s, c, p, cols, arena, pos, tiles, tile0, cb,
                        dbg);
 }
+void launch_delta_lengths(const DChunk* c, DPage* p, int n, const uint8_t* arena, int32_t* pos, int32_t* aux, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_delta_lengths, dim3(n), dim3(NT), 0, s, c, p, arena, pos, aux);
+}
+void launch_bss_gather(const DChunk* c, DPage* p, int n, const uint8_t* arena, long long* dbp, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_bss_gather, dim3(n, BSS_Y), dim3(NT), 0, s, c, p, arena, dbp);
+}
+// the delta byte-array pages among string-copy tiles [tile0, tile0 + ntiles) and pages [page0, page0 + n_pages);
+// step 0: k_dlba_copy, 1: k_dba_tail, 2: k_dba_link, 3: k_dba_expand (in this order on one stream)
+void launch_delta_copy(int step, const DChunk* c, const DPage* p, int page0, int n_pages, int ntiles, const DColumn* cols,
+                       const uint8_t* arena, const int32_t* pos, const int32_t* aux, const int2* tiles, int tile0,
+                       hipStream_t s) {
+  if (step == 2) {
+    if (n_pages) hipLaunchKernelGGL(k_dba_link, dim3(n_pages), dim3(NT), 0, s, c, p + page0, cols, pos, aux);
+    return;
+  }
+  if (!ntiles) return;
+  if (step == 0) hipLaunchKernelGGL(k_dlba_copy, dim3(ntiles), dim3(CT), 0, s, c, p, cols, arena, pos, aux, tiles, tile0);
+  else if (step == 1) hipLaunchKernelGGL(k_dba_tail, dim3(ntiles), dim3(CT), 0, s, c, p, cols, arena, pos, aux, tiles, tile0);
+  else hipLaunchKernelGGL(k_dba_expand, dim3(ntiles), dim3(CT), 0, s, c, p, cols, arena, pos, aux, tiles, tile0);
+}
 void launch_json_canon(DJsonAction* a, int n, const uint8_t* jchars, uint8_t* canon, uint32_t seed, DState* st,
                        hipStream_t s) {
   if (n) hipLaunchKernelGGL(k_json_canon, dim3((n + 255) / 256), dim3(256), 0, s, a, n, jchars, canon, seed, st);
@@ -5508,6 +5901,8 @@ int warm_kernels() {
       (const void*)k_page_headers, (const void*)k_snap_walk, (const void*)k_snap_walk_lds<false>, (const void*)k_snap_walk_lds<true>, (const void*)k_snap_link, (const void*)k_snap_recheck, (const void*)k_snap_fix, (const void*)k_snap_bounds,
       (const void*)k_snap_frag, (const void*)k_snappy_serial, (const void*)k_pos_count,
       (const void*)k_pos_scan, (const void*)k_pos_fallback, (const void*)k_delta_decode,
+      (const void*)k_delta_lengths, (const void*)k_bss_gather, (const void*)k_dlba_copy, (const void*)k_dba_tail,
+      (const void*)k_dba_link, (const void*)k_dba_expand,
       (const void*)k_page_runs, (const void*)k_tile_count, (const void*)k_tile_scan1, (const void*)k_tile_chars,
       (const void*)k_tile_scan2, (const void*)k_tile_decode, (const void*)k_string_copy, (const void*)k_stats_eval,
       (const void*)k_part_eval, (const void*)k_json_canon, (const void*)k_slots_init, (const void*)k_table_insert,

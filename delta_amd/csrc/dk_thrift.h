@@ -121,7 +121,7 @@ struct TReader {
 // Parquet enums (parquet-format)
 enum PageType { PAGE_DATA = 0, PAGE_INDEX = 1, PAGE_DICT = 2, PAGE_DATA_V2 = 3 };
 enum Encoding { ENC_PLAIN = 0, ENC_PLAIN_DICT = 2, ENC_RLE = 3, ENC_BIT_PACKED = 4, ENC_DELTA_BP = 5,
-                ENC_DELTA_LBA = 6, ENC_DELTA_BA = 7, ENC_RLE_DICT = 8 };
+                ENC_DELTA_LBA = 6, ENC_DELTA_BA = 7, ENC_RLE_DICT = 8, ENC_BYTE_STREAM_SPLIT = 9 };
 enum Phys { PT_BOOLEAN = 0, PT_INT32 = 1, PT_INT64 = 2, PT_INT96 = 3, PT_FLOAT = 4, PT_DOUBLE = 5,
             PT_BYTE_ARRAY = 6, PT_FIXED = 7 };
 enum Codec { CODEC_NONE = 0, CODEC_SNAPPY = 1 };

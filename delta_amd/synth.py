@@ -437,7 +437,34 @@ def _write_parquet(table, path, spec: TableSpec):
             "add.size", "add.modificationTime")}
     else:
         kw["use_dictionary"] = spec.use_dictionary
+    # spec.extra["column_encoding"]: {leaf path: Parquet encoding} (e.g. "add.path": "DELTA_BYTE_ARRAY");
+    # leaves the file lacks are ignored; pyarrow needs the dictionary off for the listed leaves
+    enc = spec.extra.get("column_encoding")
+    if enc:
+        have = set(_leaf_paths(table.schema))
+        enc = {k: v for k, v in enc.items() if k in have}
+        kw["column_encoding"] = dict(kw.get("column_encoding") or {}, **enc)
+        if kw["use_dictionary"] is True:
+            kw["use_dictionary"] = [c for c in have if c not in enc]
+        elif kw["use_dictionary"]:
+            kw["use_dictionary"] = [c for c in kw["use_dictionary"] if c not in enc]
     pq.write_table(table, path, **kw)
+
+
+def _leaf_paths(schema, prefix=""):
+    """Parquet leaf paths of an Arrow schema / struct type as pyarrow's writer names them."""
+    out = []
+    for f in schema:
+        t = f.type
+        if pa.types.is_struct(t):
+            out += _leaf_paths(t, prefix + f.name + ".")
+        elif pa.types.is_map(t):
+            out += [prefix + f.name + ".key_value.key", prefix + f.name + ".key_value.value"]
+        elif pa.types.is_list(t) or pa.types.is_large_list(t):
+            out += [prefix + f.name + ".list.element"]
+        else:
+            out.append(prefix + f.name)
+    return out
 
 
 def _json_add(path, day, size, mtime, dv=None, stats=None, pv_keys=1, region=None):
