@@ -8,8 +8,8 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libdkgpu.so")
 OBJ = os.path.join(HERE, "..", "build", "obj")   # kept between builds: only stale objects recompile
 SOURCES = ["dk_host.cpp", "dk_expr.cpp", "dk_comm.cpp", "dk_kernels.hip", "dk_arrow.hip", "dk_dv.hip", "dk_encode.hip",
-           "dk_export.hip", "dk_lookup.hip"]
-HEADERS = ["dk_device.h", "dk_thrift.h", "dk_uri.h", "dk_expr.h"]
+           "dk_export.hip", "dk_lookup.hip", "dk_zstd.hip"]
+HEADERS = ["dk_device.h", "dk_thrift.h", "dk_uri.h", "dk_expr.h", "dk_zstd.h"]
 
 
 def _stale():

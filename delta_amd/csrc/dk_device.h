@@ -21,7 +21,7 @@ struct DChunk {
 // by the host plan, so k_tile_decode tests one bit where it tested one encoding.
 enum : int32_t { PF_DICT = 1, PF_POS = 2, PF_SLOT64 = 4 };
 enum : int32_t { PS_OK = 0, PS_BAD_HEADER = 1, PS_BAD_LEVELS = 2, PS_BAD_VALUES = 3,
-                 PS_UNSUPPORTED = 4, PS_BAD_DICT = 5, PS_BAD_SNAPPY = 6 };
+                 PS_UNSUPPORTED = 4, PS_BAD_DICT = 5, PS_BAD_SNAPPY = 6, PS_BAD_ZSTD = 7 };
 
 struct DPage {
   int64_t hdr_off;       // offset of the page header in the packed chunk image (input)

@@ -30,11 +30,13 @@
 #include "dk_thrift.h"
 #include "dk_uri.h"
 #include "dk_expr.h"
+#include "dk_zstd.h"
 
 namespace dk {
 void launch_page_headers(const DChunk*, DPage*, int, hipStream_t);
 void launch_snappy(const SnapCtx&, int, int, const int2*, int, hipStream_t);
 void snap_stats(unsigned long long*);
+void launch_zstd(const DChunk*, DPage*, uint8_t*, const int32_t*, const int64_t*, uint8_t*, int, hipStream_t);
 void launch_pack_bits(const uint8_t*, long long, uint8_t*, hipStream_t);
 void launch_expand(const int64_t*, const int32_t*, int, int, void*, hipStream_t);
 void launch_copy_zc(void*, const void*, long long, hipStream_t);
@@ -1040,13 +1042,13 @@ static int phys_width(int phys, int tl) {
 // kernel timing (HIP events on the engine stream)
 // ------------------------------------------------------------------------------------------------
 struct KTimer {
-  static constexpr int K = 29;
+  static constexpr int K = 30;
   const char* names[K] = {"k_page_headers", "k_delta_lengths", "k_tile_count", "k_tile_scan",
                           "k_string_positions", "k_tile_decode", "k_string_copy", "k_json_canon",
                           "k_table_insert", "k_table_update", "k_json_select", "k_probe", "step_total",
                           "k_snap_walk_link", "k_delta_decode", "k_page_runs", "k_tile_chars", "k_stats_eval", "k_part_eval",
                           "k_snap_fix", "k_snap_frag", "k_snappy_serial", "k_owner_route", "k_owner_resolve",
-                          "k_bss_gather", "k_dlba_copy", "k_dba_tail", "k_dba_link", "k_dba_expand"};
+                          "k_bss_gather", "k_dlba_copy", "k_dba_tail", "k_dba_link", "k_dba_expand", "k_zstd_page"};
   double sum_ms[K] = {0};
   int64_t cnt[K] = {0};
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
@@ -1135,6 +1137,9 @@ struct dk_parquet {
   DBuf d_sbase, d_spage, d_snapws;   // speculative-walk segments: page bases, owner page, workspace
   DBuf d_tbits;                      // page mode: tag-start bitmap (DK_SNAP_SEG / 64 words per segment)
   DBuf d_pwork;                      // page-mode work items (page, -1)
+  // zstd: compressed pages (one wave each), their offsets in the literals / sequence-list scratch
+  DBuf d_zpage, d_zoff, d_zscratch;
+  std::vector<int32_t> h_zpage;
   int n_cpages = 0, n_frags = 0, n_segs = 0;
   DBuf d_ltiles, d_runs;     // level tiles (DTile) and hybrid-stream run tables (Seg)
   int n_ltiles = 0;
@@ -1234,7 +1239,7 @@ static bool snap_hybrid(const dk_parquet* p) {
 // [ca, cb) with their segments [s0, s1) and fragments [fr0, fr1), columns [col0, col1), level tiles
 // [t0, t1) and string-position chunks [pc0, pc1). The prepare pass runs one slice per group of files
 // as soon as those files' H2D copies have landed.
-struct PRange { int pa = 0, pb = 0, ca = 0, cb = 0, s0 = 0, s1 = 0, fr0 = 0, fr1 = 0, col0 = 0, col1 = 0, t0 = 0, t1 = 0, pc0 = 0, pc1 = 0; };
+struct PRange { int pa = 0, pb = 0, ca = 0, cb = 0, za = 0, zb = 0, s0 = 0, s1 = 0, fr0 = 0, fr1 = 0, col0 = 0, col1 = 0, t0 = 0, t1 = 0, pc0 = 0, pc1 = 0; };
 
 static PRange file_range(const dk_parquet* p, int f0, int f1) {
   PRange R;
@@ -1242,6 +1247,8 @@ static PRange file_range(const dk_parquet* p, int f0, int f1) {
   R.col0 = p->file_col0[f0]; R.col1 = p->file_col0[f1];
   R.ca = (int)(std::lower_bound(p->h_cpage.begin(), p->h_cpage.end(), R.pa) - p->h_cpage.begin());
   R.cb = (int)(std::lower_bound(p->h_cpage.begin(), p->h_cpage.end(), R.pb) - p->h_cpage.begin());
+  R.za = (int)(std::lower_bound(p->h_zpage.begin(), p->h_zpage.end(), R.pa) - p->h_zpage.begin());
+  R.zb = (int)(std::lower_bound(p->h_zpage.begin(), p->h_zpage.end(), R.pb) - p->h_zpage.begin());
   if (!p->h_sbase.empty()) { R.s0 = p->h_sbase[R.ca]; R.s1 = p->h_sbase[R.cb]; R.fr0 = p->h_fbase[R.ca]; R.fr1 = p->h_fbase[R.cb]; }
   R.t0 = R.col0 < p->n_cols ? p->h_cols[R.col0].first_tile : p->n_ltiles;
   R.t1 = R.col1 < p->n_cols ? p->h_cols[R.col1].first_tile : p->n_ltiles;
@@ -1287,6 +1294,11 @@ static void sizing_stages(dk_parquet* p, hipStream_t s, const PRange& R) {
     { KTimer::Scope s1(&T, 19, s); launch_snappy(X, ncp, nfr, wk, 1, s); }
     { KTimer::Scope s2(&T, 20, s); launch_snappy(X, ncp, nfr, wk, 2, s); }
     { KTimer::Scope s3(&T, 21, s); launch_snappy(X, ncp, nfr, wk, 3, s); }
+  }
+  if (R.zb > R.za) {                               // zstd pages: one wave each, into the same arena
+    KTimer::Scope sc(&T, 29, s);
+    launch_zstd(C, P, p->d_arena.as<uint8_t>(), p->d_zpage.as<int32_t>() + R.za, p->d_zoff.as<int64_t>() + R.za,
+                p->d_zscratch.as<uint8_t>(), R.zb - R.za, s);
   }
   { KTimer::Scope sc(&T, 15, s); launch_page_runs(C, P + R.pa, np, arena, runs, s); }
   { KTimer::Scope sc(&T, 2, s); launch_tile_count(C, P, arena, runs, LT, R.t1 - R.t0, R.t0, s); }
@@ -1387,8 +1399,8 @@ static std::string page_status_msg(const dk_parquet* p, const std::vector<DPage>
       const DChunk& ck = p->h_chunks[pg.chunk];
       int fi = p->col_file[ck.col];
       static const char* why[] = {"ok", "bad page header", "bad levels", "bad values", "unsupported encoding/codec",
-                                  "bad dictionary", "bad snappy block"};
-      return "Error reading Parquet file: " + p->files[fi].path + " (" + why[pg.status < 7 ? pg.status : 4] +
+                                  "bad dictionary", "bad snappy block", "bad zstd frame"};
+      return "Error reading Parquet file: " + p->files[fi].path + " (" + why[pg.status < 8 ? pg.status : 4] +
              " at offset " + std::to_string(file_offset(p->files[fi], pg.hdr_off)) + ")";
     }
   return "";
@@ -1665,13 +1677,15 @@ static int prepare(dk_parquet* p) {
   // per-page work lists (fragments, segments, level tiles, position chunks) are expanded on the device
   // from per-group counts (k_expand): the host only builds the prefix arrays (one entry per page)
   std::vector<int32_t> cpage, fbase(1, 0), sbase(1, 0);
+  std::vector<int32_t> zpage;                // zstd pages and their scratch offsets (dk_zstd.h)
+  std::vector<int64_t> zoff(1, 0);
   for (size_t i = 0; i < p->h_pages.size(); i++) {
     DPage& pg = p->h_pages[i];
     DChunk& ck = p->h_chunks[pg.chunk];
     pg.unc_off = -1;
     pg.flags &= PF_DICT;                     // PF_POS / PF_SLOT64: set below
     if (ck.codec != CODEC_NONE) {
-      if (ck.codec != CODEC_SNAPPY)
+      if (ck.codec != CODEC_SNAPPY && ck.codec != CODEC_ZSTD)
         return fail("Error reading Parquet file: " + p->files[p->col_file[ck.col]].path +
                     " (unsupported compression codec " + std::to_string(ck.codec) + ")");
       if (!(pg.ptype == PAGE_DATA_V2 && !pg.is_comp)) {
@@ -1680,14 +1694,19 @@ static int prepare(dk_parquet* p) {
         // page's region is padded to 16 bytes (k_snap_frag stores whole dwordx4 granules)
         pg.unc_off = ((arena_n + lv + 15) & ~(int64_t)15) - lv;
         arena_n = (pg.unc_off + (int64_t)pg.usize + 15) & ~(int64_t)15;
-        p->has_compressed = true;
         const int64_t body = pg.usize > lv ? pg.usize - lv : 0;
-        const int nf = body > 0 ? (int)((body + 65535) / 65536) : 1;   // k_snap_frag fragments (64 KiB)
-        const int64_t cbody = pg.csize > lv ? pg.csize - lv : 0;
-        const int ns = cbody > 0 ? (int)((cbody + DK_SNAP_SEG - 1) / DK_SNAP_SEG) : 1;
-        sbase.push_back(sbase.back() + ns);
-        cpage.push_back((int32_t)i);
-        fbase.push_back(fbase.back() + nf);
+        if (ck.codec == CODEC_ZSTD) {          // a work list of its own: h_cpage / sbase / fbase are snappy's
+          zpage.push_back((int32_t)i);
+          zoff.push_back(zoff.back() + zs_scratch_bytes(body));
+        } else {
+          p->has_compressed = true;
+          const int nf = body > 0 ? (int)((body + 65535) / 65536) : 1;   // k_snap_frag fragments (64 KiB)
+          const int64_t cbody = pg.csize > lv ? pg.csize - lv : 0;
+          const int ns = cbody > 0 ? (int)((cbody + DK_SNAP_SEG - 1) / DK_SNAP_SEG) : 1;
+          sbase.push_back(sbase.back() + ns);
+          cpage.push_back((int32_t)i);
+          fbase.push_back(fbase.back() + nf);
+        }
       }
       pg.status = PS_OK;
     }
@@ -1800,6 +1819,11 @@ static int prepare(dk_parquet* p) {
     // page and hybrid modes find tags through a bitmap built by the speculative walk
     if ((snap_page_mode(p) || snap_hybrid(p)) && p->d_tbits.alloc(((size_t)p->n_segs * (DK_SNAP_SEG / 64) + 4) * 8)) return 1;
   }
+  p->h_zpage = zpage;
+  if (!zpage.empty() &&
+      (upload_zc(p, p->d_zpage, zpage.data(), zpage.size() * 4, us) || upload_zc(p, p->d_zoff, zoff.data(), zoff.size() * 8, us) ||
+       p->d_zscratch.alloc((size_t)zoff.back() + 16)))
+    return 1;
   if (p->d_dbp.alloc((size_t)(dbp_n + 16) * 8)) return 1;
   p->bytes_arena = arena_n;
   if (upload_zc(p, p->d_chunks, p->h_chunks.data(), p->h_chunks.size() * sizeof(DChunk), us)) return 1;
@@ -2980,7 +3004,15 @@ extern "C" int dk_parquet_kernel_traffic(dk_parquet* p, const char* kernel, int6
         if (dba) { rd += 12ll * pg.n_values + (pg.vbytes - pg.bytes_off); wr += pg.n_chars + (key ? 8ll * pg.n_values : 0); }
       } else if (k == "k_snap_frag") {
         // snappy pages: compressed body read, decompressed body written (v2 levels excluded)
-        if (pg.unc_off >= 0) {
+        if (pg.unc_off >= 0 && p->h_chunks[pg.chunk].codec == CODEC_SNAPPY) {
+          const int64_t lv = pg.ptype == PAGE_DATA_V2 ? (int64_t)pg.rl_len + pg.dl_len : 0;
+          rd += pg.csize - lv; wr += pg.usize - lv;
+        }
+      } else if (k == "k_zstd_page") {
+        // zstd pages: compressed body read, decompressed body written; the literals go through the
+        // scratch once more (written and read: at most the body) and each match reads what it copies --
+        // a lower bound that counts the body once each way
+        if (pg.unc_off >= 0 && p->h_chunks[pg.chunk].codec == CODEC_ZSTD) {
           const int64_t lv = pg.ptype == PAGE_DATA_V2 ? (int64_t)pg.rl_len + pg.dl_len : 0;
           rd += pg.csize - lv; wr += pg.usize - lv;
         }
@@ -3006,7 +3038,13 @@ extern "C" int dk_parquet_kernel_traffic(dk_parquet* p, const char* kernel, int6
       for (const DChunk& ck : p->h_chunks)
         if (ck.col == (int)ci && ck.dict_page >= 0) {
           const DPage& d = p->h_pages[ck.dict_page];
-          if (d.unc_off >= 0) { rd += d.csize; wr += d.usize; }
+          if (d.unc_off >= 0 && ck.codec == CODEC_SNAPPY) { rd += d.csize; wr += d.usize; }
+        }
+    if (k == "k_zstd_page")                                      // zstd dictionary pages
+      for (const DChunk& ck : p->h_chunks)
+        if (ck.col == (int)ci && ck.dict_page >= 0) {
+          const DPage& d = p->h_pages[ck.dict_page];
+          if (d.unc_off >= 0 && ck.codec == CODEC_ZSTD) { rd += d.csize; wr += d.usize; }
         }
     if (k == "k_tile_decode")                                     // dictionary pages (read once)
       for (const DChunk& ck : p->h_chunks)

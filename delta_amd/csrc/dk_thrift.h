@@ -124,7 +124,7 @@ enum Encoding { ENC_PLAIN = 0, ENC_PLAIN_DICT = 2, ENC_RLE = 3, ENC_BIT_PACKED =
                 ENC_DELTA_LBA = 6, ENC_DELTA_BA = 7, ENC_RLE_DICT = 8, ENC_BYTE_STREAM_SPLIT = 9 };
 enum Phys { PT_BOOLEAN = 0, PT_INT32 = 1, PT_INT64 = 2, PT_INT96 = 3, PT_FLOAT = 4, PT_DOUBLE = 5,
             PT_BYTE_ARRAY = 6, PT_FIXED = 7 };
-enum Codec { CODEC_NONE = 0, CODEC_SNAPPY = 1 };
+enum Codec { CODEC_NONE = 0, CODEC_SNAPPY = 1, CODEC_ZSTD = 6 };
 
 struct PageHeader {
   int32_t type, usize, csize, num_values, enc, dl_enc, rl_enc, dl_len, rl_len, is_comp, hdr_len, ok;

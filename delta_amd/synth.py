@@ -448,6 +448,8 @@ def _write_parquet(table, path, spec: TableSpec):
             kw["use_dictionary"] = [c for c in have if c not in enc]
         elif kw["use_dictionary"]:
             kw["use_dictionary"] = [c for c in kw["use_dictionary"] if c not in enc]
+    if spec.extra.get("compression_level") is not None:       # the codec's level (zstd: parquet-mr's default is 3)
+        kw["compression_level"] = spec.extra["compression_level"]
     pq.write_table(table, path, **kw)
 
 
