@@ -149,7 +149,7 @@ EXPORTS = ["dk_last_error", "dk_version", "dk_engine_create", "dk_engine_destroy
            "dk_comm_create_local", "dk_comm_world", "dk_comm_rank", "dk_comm_allreduce_i64", "dk_comm_alltoallv",
            "dk_comm_abort", "dk_comm_last_run", "dk_comm_last_steps", "dk_comm_destroy", "dk_replay_owner_run", "dk_owner_protocol_run",
            "dk_replay_scan_open", "dk_scan_next", "dk_scan_stats", "dk_scan_close",
-           "dk_data_compile", "dk_data_scan_open"]
+           "dk_data_compile", "dk_data_scan_open", "dk_parquet_snappy_serial"]
 
 
 def lib(build_if_missing=True):
@@ -190,6 +190,7 @@ def lib(build_if_missing=True):
         "dk_parquet_nonnull_rows": (C.c_int, [P, I32, I32, I32, I64, P, I64, C.POINTER(I64)]),
         "dk_parquet_traffic": (C.c_int, [P, C.POINTER(I64), C.POINTER(I64)]),
         "dk_parquet_kernel_traffic": (C.c_int, [P, C.c_char_p, C.POINTER(I64), C.POINTER(I64)]),
+        "dk_parquet_snappy_serial": (C.c_int, [P, C.POINTER(I64), C.POINTER(I64)]),
         "dk_parquet_close": (None, [P]),
         "dk_json_tail_parse": (C.c_int, [P, C.POINTER(C.c_char_p), C.POINTER(I64), I32, I32, C.POINTER(P)]),
         "dk_json_tail_rows": (I64, [P]),

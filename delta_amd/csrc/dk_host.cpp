@@ -2932,6 +2932,21 @@ extern "C" int dk_parquet_traffic(dk_parquet* p, int64_t* r, int64_t* w) {
   *r = p->bytes_read; *w = p->bytes_written; return 0;
 }
 
+// Which snappy path decoded the pages of the last prepare: the compressed snappy pages and how many
+// of them k_snap_fix / k_snap_bounds / k_snap_frag flagged for k_snappy_serial. Copies d_serial back
+// when asked (tests/test_snappy_craft.py); the decode itself does nothing for it.
+extern "C" int dk_parquet_snappy_serial(dk_parquet* p, int64_t* n_pages, int64_t* n_serial) {
+  if (ensure_open(p)) return 1;
+  *n_pages = p->n_cpages; *n_serial = 0;
+  if (!p->n_cpages) return 0;
+  hipSetDevice(p->eng->cfg.device);
+  HIPOK(hipStreamSynchronize(p->stream));
+  std::vector<int32_t> h((size_t)p->n_cpages);
+  HIPOK(hipMemcpy(h.data(), p->d_serial.p, h.size() * 4, hipMemcpyDeviceToHost));
+  for (int32_t v : h) *n_serial += v != 0;
+  return 0;
+}
+
 // Algorithmic bytes of one launch of a decode kernel ("Roofline"): what the kernel must
 // read and write at minimum, from the page / column metadata of the last prepare.
 extern "C" int dk_parquet_kernel_traffic(dk_parquet* p, const char* kernel, int64_t* r, int64_t* w) {

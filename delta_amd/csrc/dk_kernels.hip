@@ -1401,16 +1401,11 @@ __global__ __launch_bounds__(64) void k_snappy_serial(const DChunk* __restrict__
     for (int64_t i = lane; i < clen; i += 64) out[i] = in[i];
     return;
   }
-  // preamble: varint uncompressed length
-  int64_t p = 0;
+  // preamble: varint uncompressed length (a varint cut off by the stream end, or still continuing
+  // after five bytes, is malformed whatever its low bits spell)
   uint64_t n = 0;
-  for (int s = 0; s < 35; s += 7) {
-    if (p >= clen) break;
-    uint8_t b = in[p++];
-    n |= (uint64_t)(b & 0x7f) << s;
-    if (!(b & 0x80)) break;
-  }
-  bool bad = (int64_t)n != ulen;
+  int64_t p = snap_preamble(in, clen, &n);
+  bool bad = p < 0 || (int64_t)n != ulen;
   int64_t o = 0, fenced = 0;
   while (!bad && p < clen) {
     const uint8_t tag = in[p++];

@@ -241,6 +241,12 @@ class ParquetSet:
         check(lib().dk_parquet_traffic(self._h, C.byref(r), C.byref(w)))
         return r.value, w.value
 
+    def snappy_serial(self):
+        """(snappy pages, pages among them that went to the serial decoder) of the last decode."""
+        n, s = C.c_int64(), C.c_int64()
+        check(lib().dk_parquet_snappy_serial(self._h, C.byref(n), C.byref(s)))
+        return n.value, s.value
+
     def kernel_traffic(self, kernel):
         """Algorithmic (read, written) bytes of one launch of a decode kernel."""
         r, w = C.c_int64(), C.c_int64()

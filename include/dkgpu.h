@@ -167,6 +167,10 @@ int  dk_parquet_column_rows(dk_parquet* p, int32_t file, int32_t leaf, int64_t r
 int  dk_parquet_open_ms(dk_parquet* p, double out[7]);
 /* bytes read (projected column chunks) and written (decoded buffers) per decode, for roofline */
 int  dk_parquet_traffic(dk_parquet* p, int64_t* bytes_read, int64_t* bytes_written);
+/* snappy pages of the set and how many of them the fragment decoder handed to the serial decoder
+ * (a tag straddling a 64 KiB output boundary, a copy reaching back across one, or a page-mode
+ * failure); copied back from the device on demand, after a decode */
+int  dk_parquet_snappy_serial(dk_parquet* p, int64_t* n_pages, int64_t* n_serial);
 /* algorithmic bytes one launch of a decode kernel must move ("k_string_copy", "k_tile_decode") */
 int  dk_parquet_kernel_traffic(dk_parquet* p, const char* kernel, int64_t* bytes_read, int64_t* bytes_written);
 void dk_parquet_close(dk_parquet* p);
