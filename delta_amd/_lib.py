@@ -60,6 +60,12 @@ class dk_scan_options(C.Structure):
     _fields_ = [("compact", C.c_int32), ("batch_rows", C.c_int32), ("window_rows", C.c_int32)]
 
 
+class dk_rank_scan_options(C.Structure):
+    _fields_ = [("compact", C.c_int32), ("batch_rows", C.c_int32), ("window_rows", C.c_int32),
+                ("emit_tail", C.c_int32), ("n_ckpt_files", C.c_int32), ("n_tail_files", C.c_int32),
+                ("ckpt_index", C.POINTER(C.c_int32)), ("tail_index", C.POINTER(C.c_int32))]
+
+
 class dk_data_options(C.Structure):
     _fields_ = [("field_ids", C.c_void_p), ("predicate", C.c_void_p), ("dvs", C.c_void_p), ("dv_index", C.c_void_p),
                 ("filter", C.c_void_p), ("compact", C.c_int32), ("batch_rows", C.c_int32), ("window_rows", C.c_int32)]
@@ -149,7 +155,9 @@ EXPORTS = ["dk_last_error", "dk_version", "dk_engine_create", "dk_engine_destroy
            "dk_comm_create_local", "dk_comm_world", "dk_comm_rank", "dk_comm_allreduce_i64", "dk_comm_alltoallv",
            "dk_comm_abort", "dk_comm_last_run", "dk_comm_last_steps", "dk_comm_destroy", "dk_replay_owner_run", "dk_owner_protocol_run",
            "dk_replay_scan_open", "dk_scan_next", "dk_scan_stats", "dk_scan_close",
-           "dk_data_compile", "dk_data_scan_open", "dk_parquet_snappy_serial"]
+           "dk_data_compile", "dk_data_scan_open", "dk_parquet_snappy_serial",
+           "dk_replay_scan_open_rank", "dk_scan_batch_order", "dk_scan_batch_selection", "dk_scan_merge_open",
+           "dk_scan_merge_next", "dk_scan_merge_close", "dk_replay_counters_sum"]
 
 
 def lib(build_if_missing=True):
@@ -231,6 +239,14 @@ def lib(build_if_missing=True):
         "dk_scan_next": (C.c_int, [P, C.POINTER(C.POINTER(dk_batch)), C.POINTER(P)]),
         "dk_scan_stats": (C.c_int, [P, C.POINTER(I64)]),
         "dk_scan_close": (None, [P]),
+        "dk_replay_scan_open_rank": (C.c_int, [P, C.POINTER(C.c_char_p), I32, C.POINTER(dk_rank_scan_options),
+                                               C.POINTER(P)]),
+        "dk_scan_batch_order": (C.c_int, [C.POINTER(dk_batch), C.POINTER(I64)]),
+        "dk_scan_batch_selection": (C.c_int, [C.POINTER(dk_batch), C.POINTER(P)]),
+        "dk_scan_merge_open": (C.c_int, [C.POINTER(P), I32, C.POINTER(P)]),
+        "dk_scan_merge_next": (C.c_int, [P, C.POINTER(C.POINTER(dk_batch)), C.POINTER(I32)]),
+        "dk_scan_merge_close": (None, [P]),
+        "dk_replay_counters_sum": (C.c_int, [C.POINTER(P), I32, C.POINTER(I64)]),
         "dk_data_compile": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(P)]),
         "dk_data_scan_open": (C.c_int, [P, C.POINTER(C.c_char_p), I32, C.POINTER(C.c_char_p), I32,
                                         C.POINTER(dk_data_options), C.POINTER(P)]),

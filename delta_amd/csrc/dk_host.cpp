@@ -6065,6 +6065,9 @@ struct dk_batch_impl {
   std::vector<dk_batch_column> cols;
   BatchOwner* rd;
   RWin* win;
+  const uint8_t* sel = nullptr;  // scan readers, compact = 0: the batch's selection bytes (in its window)
+  bool has_order = false;        // rank readers (dk_replay_scan_open_rank): the batch's order key
+  int64_t order[3] = {0, 0, 0};
 };
 
 static void reader_maybe_free(BatchOwner* r, std::unique_lock<std::mutex>& lk) {
@@ -6408,7 +6411,10 @@ extern "C" int64_t dk_reader_num_rows(dk_reader* r, int32_t file) {
 // runs on the reader's own stream, ordered after the replay's stream by an event.
 // ------------------------------------------------------------------------------------------------
 namespace {
-struct ScanSrc { int file; int64_t a, b; };   // file >= 0: checkpoint file; -1 tail / -2 manifest: tail rows [a, b)
+// file >= 0: checkpoint file; -1 tail / -2 manifest: tail rows [a, b). A rank reader's sources also carry
+// their order key: the source's replay-order index in the whole scan and the source row of row 0
+// (a checkpoint file: the file row of the rank's row-group run)
+struct ScanSrc { int file; int64_t a, b; int64_t gidx = 0, row_base = 0; };
 int grow(DBuf& d, size_t n) { return d.n >= n && d.p ? 0 : d.alloc(n); }
 int grow(HBuf& h, size_t n) { return h.size() >= n && h.data() ? 0 : h.alloc(n); }
 }  // namespace
@@ -6432,6 +6438,8 @@ struct dk_scan_reader : BatchOwner {
   DBuf d_rows, d_wcnt, d_wbase, d_sums, d_total, d_stage, d_ovf, d_cnt, d_ent;
   HBuf h_rng, h_tot;
   int64_t stats[4] = {0, 0, 0, 0};   // D2H bytes, windows, rows, batches
+  bool rank = false;                 // dk_replay_scan_open_rank: this rank's own rows, batches carry order keys
+  bool merged = false;               // a dk_scan_merge pulls from it
   // data-row reader (dk_data_scan_open): its own decoded set instead of a replay's checkpoint; the
   // first leaves.size() leaves of the set are the emitted ones, the rest only feed the filter
   bool data = false;
@@ -6458,6 +6466,52 @@ static void replay_drop_scans(dk_replay* r) {
   r->scans.clear();
 }
 
+// What dk_replay_scan_open and dk_replay_scan_open_rank share. First half, no device work: the
+// reader's sizes and its leaves resolved against the replay's projection.
+static int scan_open_leaves(dk_scan_reader* s, dk_replay* r, const char* const* leaves, int32_t n_leaves, int compact,
+                            int32_t batch_rows, int32_t window_rows, const char* who) {
+  s->eng = r->eng; s->rp = r;
+  s->compact = compact != 0;
+  s->B = batch_rows > 0 ? batch_rows : (r->eng->cfg.parquet_batch_size > 0 ? r->eng->cfg.parquet_batch_size : 1024);
+  if (window_rows > 0) s->W = window_rows;
+  s->W = std::max<int64_t>(s->B, s->W / s->B * s->B);
+  for (int i = 0; i < n_leaves; i++) {
+    if (!leaves[i]) return fail(std::string(who) + ": null leaf");
+    int pl = -1, jl = -1;
+    if (r->ck) for (size_t k = 0; k < r->ck->leaves.size(); k++) if (r->ck->leaves[k] == leaves[i]) pl = (int)k;
+    for (int k = 0; k < JL_N; k++) if (!strcmp(JSON_LEAVES[k], leaves[i])) jl = k;
+    if (r->ck ? pl < 0 : jl < 0) return fail(std::string(who) + ": leaf not projected: " + leaves[i]);
+    if (jl == JL_STATS && r->tail && !r->tail->with_stats) jl = -1;
+    if (jl >= JL_RPATH) jl = -1;               // scan files are add rows
+    s->leaves.push_back(leaves[i]); s->pleaf.push_back(pl); s->jleaf.push_back(jl);
+  }
+  return 0;
+}
+
+// Second half: the reader's stream, ordered after the replay's, and the commit tail's selection (one
+// byte per action on the device -> one per tail row)
+static int scan_open_device(dk_scan_reader* s, dk_replay* r) {
+  if (s->own.create()) return 1;
+  if (hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) return fail("hipEventCreate failed");
+  const hipStream_t st = s->own.s;
+  HIPOK(hipEventRecord(s->ev, r->stream));
+  HIPOK(hipStreamWaitEvent(st, s->ev, 0));
+  if (s->d_ovf.alloc(16) || s->d_total.alloc(64)) return 1;
+  if (r->ck && ensure_open(r->ck)) return 1;
+  if (r->tail && r->tail->rows > 0) {
+    s->tsel.assign((size_t)r->tail->rows, 0);
+    const size_t na = r->acts.size();
+    if (na) {
+      if (grow(s->h_tot, na + 64)) return 1;
+      HIPOK(hipMemcpyAsync(s->h_tot.data(), r->d_jsel.p, na, hipMemcpyDeviceToHost, st));
+      HIPOK(hipStreamSynchronize(st));
+      const uint8_t* js = s->h_tot.data();
+      for (size_t i = 0; i < na; i++) if (r->acts[i].kind != JA_REMOVE && js[i]) s->tsel[(size_t)r->act_row[i]] = 1;
+    }
+  }
+  return 0;
+}
+
 extern "C" int dk_replay_scan_open(dk_replay* r, const char* const* leaves, int32_t n_leaves, const dk_scan_options* opt,
                                    dk_scan_reader** out) {
   if (!out) return fail("dk_replay_scan_open: null out");
@@ -6469,44 +6523,77 @@ extern "C" int dk_replay_scan_open(dk_replay* r, const char* const* leaves, int3
   if (n_leaves < 0 || (n_leaves > 0 && !leaves)) return fail("dk_replay_scan_open: bad leaves");
   hipSetDevice(r->eng->cfg.device);
   std::unique_ptr<dk_scan_reader> s(new dk_scan_reader());
-  s->eng = r->eng; s->rp = r;
-  s->compact = !opt || opt->compact != 0;
-  s->B = opt && opt->batch_rows > 0 ? opt->batch_rows : (r->eng->cfg.parquet_batch_size > 0 ? r->eng->cfg.parquet_batch_size : 1024);
-  if (opt && opt->window_rows > 0) s->W = opt->window_rows;
-  s->W = std::max<int64_t>(s->B, s->W / s->B * s->B);
-  for (int i = 0; i < n_leaves; i++) {
-    if (!leaves[i]) return fail("dk_replay_scan_open: null leaf");
-    int pl = -1, jl = -1;
-    if (r->ck) for (size_t k = 0; k < r->ck->leaves.size(); k++) if (r->ck->leaves[k] == leaves[i]) pl = (int)k;
-    for (int k = 0; k < JL_N; k++) if (!strcmp(JSON_LEAVES[k], leaves[i])) jl = k;
-    if (r->ck ? pl < 0 : jl < 0) return fail(std::string("dk_replay_scan_open: leaf not projected: ") + leaves[i]);
-    if (jl == JL_STATS && r->tail && !r->tail->with_stats) jl = -1;
-    if (jl >= JL_RPATH) jl = -1;               // scan files are add rows
-    s->leaves.push_back(leaves[i]); s->pleaf.push_back(pl); s->jleaf.push_back(jl);
-  }
-  if (s->own.create()) return 1;
-  if (hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) return fail("hipEventCreate failed");
-  const hipStream_t st = s->own.s;
-  HIPOK(hipEventRecord(s->ev, r->stream));
-  HIPOK(hipStreamWaitEvent(st, s->ev, 0));
-  if (s->d_ovf.alloc(16) || s->d_total.alloc(64)) return 1;
-  if (r->ck && ensure_open(r->ck)) return 1;
-  // the commit tail's selection (one byte per action on the device -> one per tail row)
+  if (scan_open_leaves(s.get(), r, leaves, n_leaves, !opt || opt->compact != 0, opt ? opt->batch_rows : 0,
+                       opt ? opt->window_rows : 0, "dk_replay_scan_open")) return 1;
+  if (scan_open_device(s.get(), r)) return 1;
   if (r->tail && r->tail->rows > 0) {
-    s->tsel.assign((size_t)r->tail->rows, 0);
-    const size_t na = r->acts.size();
-    if (na) {
-      if (grow(s->h_tot, na + 64)) return 1;
-      HIPOK(hipMemcpyAsync(s->h_tot.data(), r->d_jsel.p, na, hipMemcpyDeviceToHost, st));
-      HIPOK(hipStreamSynchronize(st));
-      const uint8_t* js = s->h_tot.data();
-      for (size_t i = 0; i < na; i++) if (r->acts[i].kind != JA_REMOVE && js[i]) s->tsel[(size_t)r->act_row[i]] = 1;
-    }
     const int64_t r0 = r->tail->ckpt_row0 >= 0 ? r->tail->ckpt_row0 : r->tail->rows;
     if (r0 > 0) s->src.push_back({-1, 0, r0});
     if (r0 < r->tail->rows) s->src.push_back({-2, r0, r->tail->rows});
   }
   if (r->ck) for (int f = 0; f < (int)r->ck->files.size(); f++) s->src.push_back({f, 0, r->ck->files[f].num_rows});
+  {
+    std::lock_guard<std::mutex> g(r->scan_mu);
+    r->scans.push_back(s.get());
+  }
+  *out = s.release();
+  return 0;
+}
+
+// The rank reader of a sharded scan (include/dkgpu.h): the same reader over an owner or
+// exchange replay's result, restricted to what this rank is the origin of. Owner mode leaves the final
+// selection where the plain run does -- one byte per checkpoint row in d_csel[file] (k_a2a_apply,
+// k_own_cand_finish, then the partition / skipping filters) and one per commit-tail action in d_jsel
+// (k_own_tail_finish) -- so the selected-row lists and gathers of dk_export.hip serve it unchanged.
+// Every parsed tail file is a source of its own (a tail batch never spans two commit files), and each
+// source carries its order key.
+extern "C" int dk_replay_scan_open_rank(dk_replay* r, const char* const* leaves, int32_t n_leaves,
+                                        const dk_rank_scan_options* opt, dk_scan_reader** out) {
+  static const char* who = "dk_replay_scan_open_rank";
+  if (!out) return fail(std::string(who) + ": null out");
+  *out = nullptr;
+  if (!r) return fail(std::string(who) + ": null replay");
+  if (r->ow <= 0 && r->xw <= 0)
+    return fail(std::string(who) + ": the replay is neither in owner nor in exchange mode (dk_replay_set_owner / "
+                "dk_replay_set_exchange); dk_replay_scan_open reads a plain replay");
+  if (r->ow > 0 ? (r->ophase != OP_DONE || !r->have_result) : (r->xphase != 3 || !r->have_result))
+    return fail(std::string(who) + (r->ow > 0 ? ": the owner protocol has not finished (dk_replay_owner_run, then dk_replay_sync)"
+                                              : ": the exchange has not finished (dk_replay_exchange_finish, then dk_replay_sync)"));
+  if (!opt) return fail(std::string(who) + ": null options");
+  if (n_leaves < 0 || (n_leaves > 0 && !leaves)) return fail(std::string(who) + ": bad leaves");
+  const int32_t n_ck = r->ck ? (int32_t)r->ck->files.size() : 0;
+  const dk_json_tail* t = r->tail;
+  const int32_t n_tf = t && !t->file_row0.empty() ? (int32_t)t->file_row0.size() - 1 : 0;
+  if (opt->n_ckpt_files != n_ck || (n_ck > 0 && !opt->ckpt_index))
+    return fail(std::string(who) + ": ckpt_index has " + std::to_string(opt->n_ckpt_files) + " entries, the replay has " +
+                std::to_string(n_ck) + " checkpoint files");
+  const int32_t want_tf = r->ow > 0 ? n_tf : 0;
+  if (opt->n_tail_files != want_tf || (want_tf > 0 && !opt->tail_index))
+    return fail(std::string(who) + ": tail_index has " + std::to_string(opt->n_tail_files) + " entries, " +
+                (r->ow > 0 ? "this rank parsed " + std::to_string(n_tf) + " commit-tail files"
+                           : std::string("an exchange replay takes none (its tail is the whole tail)")));
+  for (int32_t i = 0; i < n_ck; i++) if (opt->ckpt_index[i] < 0) return fail(std::string(who) + ": negative checkpoint file index");
+  for (int32_t i = 0; i < want_tf; i++) if (opt->tail_index[i] < 0) return fail(std::string(who) + ": negative commit file index");
+  hipSetDevice(r->eng->cfg.device);
+  std::unique_ptr<dk_scan_reader> s(new dk_scan_reader());
+  s->rank = true;
+  if (scan_open_leaves(s.get(), r, leaves, n_leaves, opt->compact, opt->batch_rows, opt->window_rows, who)) return 1;
+  if (scan_open_device(s.get(), r)) return 1;
+  if (t && t->rows > 0 && (r->ow > 0 || opt->emit_tail)) {
+    const int64_t c0 = t->ckpt_row0 >= 0 ? t->ckpt_row0 : t->rows;
+    for (int32_t f = 0; f < n_tf; f++) {
+      const int64_t a = t->file_row0[f], b = t->file_row0[f + 1];
+      if (b <= a) continue;
+      ScanSrc S{a < c0 ? -1 : -2, a, b};
+      S.gidx = r->ow > 0 ? opt->tail_index[f] : f;
+      s->src.push_back(S);
+    }
+  }
+  for (int f = 0; f < n_ck; f++) {
+    ScanSrc S{f, 0, r->ck->files[f].num_rows};
+    S.gidx = opt->ckpt_index[f]; S.row_base = r->ck->files[f].row0;
+    s->src.push_back(S);
+  }
   {
     std::lock_guard<std::mutex> g(r->scan_mu);
     r->scans.push_back(s.get());
@@ -6809,8 +6896,16 @@ extern "C" int dk_scan_next(dk_scan_reader* s, dk_batch** out, const uint8_t** s
   const int64_t b0 = s->next, b1 = std::min<int64_t>(b0 + s->B, w->r0 + w->nr);
   const int64_t rb = b0 - w->r0, nb = b1 - b0;
   dk_batch_impl* b = make_batch(s, w, rb, nb);
-  b->pub.file = s->src[s->si].file;
-  if (selection && w->has_sel) *selection = w->buf.p + w->o_sel + rb;
+  const ScanSrc& S = s->src[s->si];
+  b->pub.file = S.file;
+  if (w->has_sel) b->sel = w->buf.p + w->o_sel + rb;
+  if (selection) *selection = b->sel;
+  if (s->rank) {                          // class, source, source row of the first row (dk_scan_batch_order)
+    b->has_order = true;
+    b->order[0] = S.file >= 0 ? 2 : S.file == -2 ? 1 : 0;
+    b->order[1] = S.gidx;
+    b->order[2] = S.row_base + b->pub.row_index[0];
+  }
   s->next = b1;
   s->stats[2] += nb; s->stats[3]++;
   *out = &b->pub;
@@ -6837,6 +6932,140 @@ extern "C" void dk_scan_close(dk_scan_reader* s) {
   s->closed = true;
   if (s->cur) { if (--s->cur->refs == 0) s->pool.push_back(s->cur); s->cur = nullptr; }
   reader_maybe_free(s, lk);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The ranks' streams as one ordered iterator (dk_scan_batch_order, dk_scan_merge_*):
+// a k-way merge of rank readers by their batches' order keys, on the caller's thread. It holds at
+// most one batch per reader (the next one of that reader), fetched when the reader's previous batch
+// has been handed out and the next pick needs it.
+// ------------------------------------------------------------------------------------------------
+extern "C" int dk_scan_batch_order(const dk_batch* pub, int64_t out[3]) {
+  if (!pub || !out) return fail("dk_scan_batch_order: null argument");
+  const dk_batch_impl* b = reinterpret_cast<const dk_batch_impl*>(pub);   // pub is the first member
+  if (!b->has_order) return fail("dk_scan_batch_order: the batch did not come from a rank reader (dk_replay_scan_open_rank)");
+  for (int i = 0; i < 3; i++) out[i] = b->order[i];
+  return 0;
+}
+
+extern "C" int dk_scan_batch_selection(const dk_batch* pub, const uint8_t** selection) {
+  if (!pub || !selection) return fail("dk_scan_batch_selection: null argument");
+  *selection = reinterpret_cast<const dk_batch_impl*>(pub)->sel;
+  return 0;
+}
+
+struct dk_scan_merge {
+  std::vector<dk_scan_reader*> rd;
+  std::vector<dk_batch*> head;         // per reader: its next batch (null: not fetched, or exhausted)
+  std::vector<uint8_t> done;
+  bool have_last = false;              // the last checkpoint batch handed out: source, last file row, reader
+  int64_t last_gidx = 0, last_end = 0;
+  int32_t last_rank = -1;
+};
+
+static bool order_less(const int64_t* a, const int64_t* b) {
+  for (int i = 0; i < 3; i++) if (a[i] != b[i]) return a[i] < b[i];
+  return false;
+}
+
+extern "C" int dk_scan_merge_open(dk_scan_reader* const* readers, int32_t n, dk_scan_merge** out) {
+  if (!out) return fail("dk_scan_merge_open: null out");
+  *out = nullptr;
+  if (n <= 0 || !readers) return fail("dk_scan_merge_open: no readers");
+  struct Run { int64_t gidx, lo, hi; int32_t rank; };
+  std::vector<Run> runs;
+  for (int32_t i = 0; i < n; i++) {
+    dk_scan_reader* s = readers[i];
+    if (!s) return fail("dk_scan_merge_open: null reader");
+    for (int32_t k = 0; k < i; k++) if (readers[k] == s) return fail("dk_scan_merge_open: a reader is given twice");
+    if (!s->rank) return fail("dk_scan_merge_open: reader " + std::to_string(i) + " is not a rank reader (dk_replay_scan_open_rank)");
+    if (s->closed) return fail("dk_scan_merge_open: reader " + std::to_string(i) + " is closed");
+    if (s->merged) return fail("dk_scan_merge_open: reader " + std::to_string(i) + " already feeds a merge");
+    if (s->si != 0 || s->next != 0 || s->stats[3] != 0) return fail("dk_scan_merge_open: reader " + std::to_string(i) + " has been read from");
+    for (const ScanSrc& S : s->src) if (S.file >= 0 && S.b > 0) runs.push_back({S.gidx, S.row_base, S.row_base + S.b, i});
+  }
+  // a rank's rows of one checkpoint file are one run of file rows; two ranks' runs never overlap
+  std::sort(runs.begin(), runs.end(), [](const Run& a, const Run& b) { return a.gidx != b.gidx ? a.gidx < b.gidx : a.lo < b.lo; });
+  for (size_t i = 1; i < runs.size(); i++) {
+    const Run& a = runs[i - 1];
+    const Run& b = runs[i];
+    if (a.gidx == b.gidx && b.lo < a.hi)
+      return fail("dk_scan_merge_open: readers " + std::to_string(a.rank) + " and " + std::to_string(b.rank) +
+                  " overlap in checkpoint file " + std::to_string(a.gidx) + ": file rows [" + std::to_string(a.lo) + ", " +
+                  std::to_string(a.hi) + ") and [" + std::to_string(b.lo) + ", " + std::to_string(b.hi) + ")");
+  }
+  dk_scan_merge* m = new dk_scan_merge();
+  m->rd.assign(readers, readers + n);
+  m->head.assign(n, nullptr);
+  m->done.assign(n, 0);
+  for (dk_scan_reader* s : m->rd) {     // the merge keeps its readers allocated, like a live batch
+    std::lock_guard<std::mutex> g(s->mu);
+    s->merged = true;
+    s->outstanding++;
+  }
+  *out = m;
+  return 0;
+}
+
+extern "C" int dk_scan_merge_next(dk_scan_merge* m, dk_batch** out, int32_t* rank) {
+  if (!out) return fail("dk_scan_merge_next: null out");
+  *out = nullptr;
+  if (rank) *rank = -1;
+  if (!m) return fail("dk_scan_merge_next: null merge");
+  int best = -1;
+  for (int i = 0; i < (int)m->rd.size(); i++) {
+    if (!m->head[i] && !m->done[i]) {
+      if (dk_scan_next(m->rd[i], &m->head[i], nullptr)) return 1;
+      if (!m->head[i]) m->done[i] = 1;
+    }
+    if (!m->head[i]) continue;
+    if (best < 0 || order_less(reinterpret_cast<dk_batch_impl*>(m->head[i])->order,
+                               reinterpret_cast<dk_batch_impl*>(m->head[best])->order)) best = i;
+  }
+  if (best < 0) return 0;
+  dk_batch_impl* b = reinterpret_cast<dk_batch_impl*>(m->head[best]);
+  if (b->order[0] == 2) {
+    if (m->have_last && m->last_gidx == b->order[1] && b->order[2] <= m->last_end)
+      return fail("dk_scan_merge_next: batches of checkpoint file " + std::to_string(b->order[1]) + " overlap in file rows: reader " +
+                  std::to_string(best) + " starts at row " + std::to_string(b->order[2]) + ", reader " +
+                  std::to_string(m->last_rank) + " ended at row " + std::to_string(m->last_end));
+    m->have_last = true;
+    m->last_gidx = b->order[1];
+    m->last_end = b->order[2] + (b->pub.row_index[b->pub.n_rows - 1] - b->pub.row_index[0]);
+    m->last_rank = best;
+  }
+  *out = m->head[best];
+  m->head[best] = nullptr;
+  if (rank) *rank = best;
+  return 0;
+}
+
+extern "C" void dk_scan_merge_close(dk_scan_merge* m) {
+  if (!m) return;
+  for (dk_batch* b : m->head) if (b) dk_batch_release(b);   // looked ahead, never handed out
+  for (dk_scan_reader* s : m->rd) {
+    std::unique_lock<std::mutex> lk(s->mu);
+    s->merged = false;
+    s->outstanding--;
+    reader_maybe_free(s, lk);           // (closed meanwhile, no batch left: freed now)
+  }
+  delete m;
+}
+
+extern "C" int dk_replay_counters_sum(dk_replay* const* replays, int32_t n, int64_t out[5]) {
+  if (!replays || n <= 0 || !out) return fail("dk_replay_counters_sum: no replays");
+  for (int i = 0; i < 5; i++) out[i] = 0;
+  for (int32_t k = 0; k < n; k++) {
+    const dk_replay* r = replays[k];
+    if (!r) return fail("dk_replay_counters_sum: null replay");
+    if (!r->have_result) return fail("dk_replay_counters_sum: replay " + std::to_string(k) + " has no result (dk_replay_sync)");
+    if ((r->ow > 0) != (replays[0]->ow > 0)) return fail("dk_replay_counters_sum: owner and exchange replays mixed");
+    // owner mode splits the commit tail's counters over the owners of its keys; otherwise every rank
+    // holds the whole tail's
+    const bool tail = r->ow > 0 || k == 0;
+    for (int i = 0; i < 5; i++) out[i] += (int64_t)((tail ? r->h_state.counters[i] : 0) + r->h_state.ckpt_counters[i]);
+  }
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -27,7 +27,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import (MAX_LEAF_DEPTH, Column, DkError, check, dk_batch, dk_column, dk_config, dk_data_options,
-                   dk_dv_descriptor, dk_read_options, dk_rg_filter, dk_scan_options, lib)
+                   dk_dv_descriptor, dk_rank_scan_options, dk_read_options, dk_rg_filter, dk_scan_options, lib)
 
 ADD_LEAVES = ["add.path", "add.partitionValues.key_value.key", "add.partitionValues.key_value.value",
               "add.size", "add.modificationTime", "add.dataChange",
@@ -1443,7 +1443,12 @@ class ScanFileBatch:
     the ParquetHandler reader's layout (BatchColumn: validity bits, int32 offsets). selection: bool
     per row, or None in compact mode (every row of the batch is selected); row_index: the source row
     of each row (the row within the checkpoint file, the tail or the manifest's rows); file_index:
-    the replay-order checkpoint file index, -1 for the commit tail, -2 for a V2 JSON manifest."""
+    the replay-order checkpoint file index, -1 for the commit tail, -2 for a V2 JSON manifest.
+    order: a sharded scan's batches carry their order key (dk_scan_batch_order): (source class --
+    0 commit tail, 1 JSON manifest, 2 checkpoint file --, the source's replay-order index in the whole
+    scan, the source row of the batch's first row: the file row for a checkpoint file). Sorting every
+    rank's batches by `order` gives getScanFiles' order; None on an unsharded scan's batches, which
+    come in that order already. rank: the rank a merged batch came from (shard.ScanFileMerge)."""
     columns: dict
     table_root: str
     size: int
@@ -1451,6 +1456,8 @@ class ScanFileBatch:
     row_index: np.ndarray
     file_index: int
     source: str = ""
+    order: tuple | None = None
+    rank: int = -1
 
     def selected_rows(self):
         if self.selection is None:
@@ -1461,13 +1468,36 @@ class ScanFileBatch:
 class ScanFileReader:
     """dk_scan_reader over a scan's finished replay (dk_replay_scan_open): next_raw() hands out the
     library's dk_batch (released with release()), iterating yields ScanFileBatch copies. close()
-    early is safe; batches stay valid after it."""
+    early is safe; batches stay valid after it.
 
-    def __init__(self, scan, compact=True, batch_rows=None, window_rows=0, leaves=None):
+    Over a scan built with withShard(..., owner=...) or withShard(..., exchange=...) it is the rank
+    reader (dk_replay_scan_open_rank): only the rows this rank is the origin of -- its row-group runs
+    of the checkpoint, in owner mode the commit files it parsed, in exchange mode the whole
+    (replicated) commit tail when emit_tail (default: on rank 0, and exactly one rank must) -- and
+    every batch carries its order key (ScanFileBatch.order). One process holding every rank merges
+    them with shard.ScanFileMerge / shard.merged_scan_file_batches. In a multi-process world no
+    collective is needed: each process streams its own batches to the consumer, which orders them
+    by `order` (keys are unique across the ranks; a rank's own stream is already ascending, so a
+    k-way merge by `order` with one batch buffered per rank is enough)."""
+
+    def __init__(self, scan, compact=True, batch_rows=None, window_rows=0, leaves=None, emit_tail=None):
         self.scan = scan
         self.leaves = list(leaves) if leaves is not None else ADD_LEAVES + ([STATS_LEAF] if scan.read_stats else [])
-        opt = dk_scan_options(1 if compact else 0, int(batch_rows or 0), int(window_rows or 0))
         self._h = C.c_void_p()
+        owner = getattr(scan, "owner", None)
+        self.rank_reader = owner is not None or \
+            (getattr(scan, "exchange", None) is not None and bool(scan.shard) and scan.shard[0] > 1)
+        if self.rank_reader:
+            ck = [int(i) for i in (scan.ckpt_index if scan.ckpt is not None else [])]
+            tf = [int(j) for j in scan.tail_commits + scan.tail_parts] if owner is not None else []
+            self._keep = ((C.c_int32 * max(1, len(ck)))(*ck), (C.c_int32 * max(1, len(tf)))(*tf))
+            emit = scan.shard[1] == 0 if emit_tail is None else bool(emit_tail)
+            ropt = dk_rank_scan_options(1 if compact else 0, int(batch_rows or 0), int(window_rows or 0), int(emit),
+                                        len(ck), len(tf), self._keep[0], self._keep[1])
+            check(lib().dk_replay_scan_open_rank(scan._rh, _cstrs(self.leaves), len(self.leaves), C.byref(ropt),
+                                                 C.byref(self._h)))
+            return
+        opt = dk_scan_options(1 if compact else 0, int(batch_rows or 0), int(window_rows or 0))
         check(lib().dk_replay_scan_open(scan._rh, _cstrs(self.leaves), len(self.leaves), C.byref(opt),
                                         C.byref(self._h)))
 
@@ -1497,10 +1527,15 @@ class ScanFileReader:
         else:
             source = "json-tail" if b.file == -1 else scan.snapshot._json_checkpoint_parts()[0]
             fidx = int(b.file)
+        order = None
+        if self.rank_reader:
+            key = (C.c_int64 * 3)()
+            check(lib().dk_scan_batch_order(raw, key))
+            order = (int(key[0]), int(key[1]), int(key[2]))
         return ScanFileBatch({leaf: BatchColumn(b.cols[i], n, leaf) for i, leaf in enumerate(self.leaves)},
                              scan.table_root(), n,
                              _np_view(sel, n, np.uint8).astype(bool) if sel else None,
-                             _np_view(b.row_index, n, np.int64).copy(), fidx, source)
+                             _np_view(b.row_index, n, np.int64).copy(), fidx, source, order)
 
     def __iter__(self):
         return self
@@ -1904,11 +1939,16 @@ class GpuScan:
                 out[name.value.decode()] = (avg.value, cnt.value)
         return out
 
-    def getScanFileBatches(self, engine, compact=True, batch_rows=None, window_rows=0, leaves=None):
+    def getScanFileBatches(self, engine, compact=True, batch_rows=None, window_rows=0, leaves=None, emit_tail=None):
         """Scan.getScanFiles as bounded batches in the ParquetHandler reader's layout (dk_scan_next):
         a generator of ScanFileBatch, in getScanFiles' order. compact=True yields only the selected
         rows (selection None), compact=False every row with its selection. Runs the scan first when
-        it has no result yet; the counters (self.metrics) are final before the first batch."""
+        it has no result yet; the counters (self.metrics) are final before the first batch.
+
+        A sharded scan (withShard(..., owner=...) or withShard(..., exchange=...)) yields this rank's
+        own batches, each with its `order` key (ScanFileReader); emit_tail as there. Its run is a
+        collective: every rank calls this at the same time (one process or thread per rank), or the
+        ranks of one process run first (shard.run_local) and shard.merged_scan_file_batches merges them."""
         if self.replay is None:
             self.prepare(engine)
             self.replay = True
@@ -1918,7 +1958,7 @@ class GpuScan:
             self._close_scan_readers()
             self.run()
             self.sync()
-        rd = ScanFileReader(self, compact, batch_rows, window_rows, leaves)
+        rd = ScanFileReader(self, compact, batch_rows, window_rows, leaves, emit_tail)
         self._scan_readers.add(rd)
         return self._scan_batches(rd)
 

@@ -659,3 +659,104 @@ def run_local(scans):
             raise e
     for sc in scans:
         sc.sync()
+
+
+# ------------------------------------------------------------------------------------------------
+# One ordered iterator over a sharded scan's ranks (dk_scan_merge_*)
+#
+# Every rank streams what it is the origin of (kernel.ScanFileReader over an owner or exchange scan:
+# dk_replay_scan_open_rank) and every batch carries its order key (ScanFileBatch.order). A process
+# that holds all the ranks -- the in-process world of OwnerComm.local / exchange_local -- merges the
+# streams in the library (ScanFileMerge). A multi-process world needs no collective for this: each
+# process hands its batches to the consumer, which orders them by `order`.
+# ------------------------------------------------------------------------------------------------
+class ScanFileMerge:
+    """dk_scan_merge over the rank readers (kernel.ScanFileReader) of one scan, reader i being
+    rank i's: next_raw() -> (dk_batch pointer, selection address or None, rank) in getScanFiles'
+    order, None at the end; iterating yields ScanFileBatch copies with `order` and `rank` set.
+    The merge looks at most one batch ahead per reader. close() leaves the readers open (their
+    owner closes them, before or after); batches stay valid after both."""
+
+    def __init__(self, readers):
+        import ctypes as C
+        from ._lib import check, lib
+        self.readers = list(readers)
+        hs = (C.c_void_p * max(1, len(self.readers)))(*[rd._h for rd in self.readers])
+        self._h = C.c_void_p()
+        check(lib().dk_scan_merge_open(hs, len(self.readers), C.byref(self._h)))
+
+    def next_raw(self):
+        import ctypes as C
+        from ._lib import check, dk_batch, lib
+        out, rank, sel = C.POINTER(dk_batch)(), C.c_int32(-1), C.c_void_p()
+        check(lib().dk_scan_merge_next(self._h, C.byref(out), C.byref(rank)))
+        if not out:
+            return None
+        check(lib().dk_scan_batch_selection(out, C.byref(sel)))
+        return out, sel.value, int(rank.value)
+
+    @staticmethod
+    def release(raw):
+        from ._lib import lib
+        lib().dk_batch_release(raw)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        got = self.next_raw()
+        if got is None:
+            raise StopIteration
+        raw, sel, rank = got
+        try:
+            b = self.readers[rank].batch(raw, sel)
+            b.rank = rank
+            return b
+        finally:
+            self.release(raw)
+
+    def close(self):
+        from ._lib import lib
+        if self._h:
+            lib().dk_scan_merge_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                    # noqa: BLE001 -- interpreter shutdown
+            pass
+
+
+def merged_scan_file_batches(scans, compact=True, batch_rows=None, window_rows=0, leaves=None, emit_tail_rank=0):
+    """Scan.getScanFiles of a sharded scan whose ranks all live in this process, as ONE ordered
+    generator of ScanFileBatch: `scans` are the ranks' GpuScans in rank order (withShard(world, r,
+    owner=...) or withShard(world, r, exchange=...)), run and synced (run_local, or run +
+    exchange_local + sync). Each rank streams its own rows from its replay; the library merges
+    the streams by order key (ScanFileMerge). In exchange mode rank `emit_tail_rank` emits the
+    replicated commit tail. The counters of the whole scan: merged_counters(scans)."""
+    from .kernel import ScanFileReader
+    readers, merge = [], None
+    try:
+        for r, sc in enumerate(scans):
+            rd = ScanFileReader(sc, compact, batch_rows, window_rows, leaves, emit_tail=(r == emit_tail_rank))
+            sc._scan_readers.add(rd)
+            readers.append(rd)
+        merge = ScanFileMerge(readers)
+        yield from merge
+    finally:
+        if merge is not None:
+            merge.close()
+        for rd in readers:
+            rd.close()
+
+
+def merged_counters(scans):
+    """The reference's five ScanMetrics counters of a sharded scan from its in-process ranks'
+    finished replays (dk_replay_counters_sum)."""
+    import ctypes as C
+    from ._lib import check, lib
+    hs = (C.c_void_p * max(1, len(scans)))(*[sc._rh for sc in scans])
+    out = (C.c_int64 * 5)()
+    check(lib().dk_replay_counters_sum(hs, len(scans), out))
+    return tuple(int(x) for x in out)

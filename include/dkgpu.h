@@ -445,7 +445,8 @@ int  dk_replay_ckpt_selection_bits_all(dk_replay* r, void* dst, const int64_t* o
  *             without a checkpoint the commit tail's), by the same dotted names; an unknown leaf fails
  *             the open.
  *  Requires   a result: dk_replay_sync has returned 0 since the last dk_replay_run*, else the open
- *             fails. Owner and exchange replays (dk_replay_set_owner / _set_exchange) are refused.
+ *             fails. Owner and exchange replays (dk_replay_set_owner / _set_exchange) are refused here:
+ *             dk_replay_scan_open_rank below streams them.
  *  Lifetime   as dk_reader: single-threaded like a Kernel iterator; a batch stays valid until
  *             dk_batch_release (from any thread), also after dk_scan_close; closing early is safe. The
  *             reader must be closed before the next dk_replay_run* or dk_replay_free: dk_scan_next
@@ -470,6 +471,68 @@ int  dk_scan_next(dk_scan_reader* s, dk_batch** out, const uint8_t** selection);
 /* so far: [0] bytes copied from the device, [1] windows loaded, [2] rows and [3] batches emitted */
 int  dk_scan_stats(dk_scan_reader* s, int64_t out[4]);
 void dk_scan_close(dk_scan_reader* s);
+
+/* ---- Scan-file batches of a sharded scan: every rank streams what it is the origin of, and the
+ * batches' order keys merge the ranks' streams into Scan.getScanFiles' one ordered iterator (Appendix
+ * B's order).
+ * dk_replay_scan_open_rank opens a dk_scan_reader over a FINISHED owner replay (dk_replay_owner_run,
+ * then dk_replay_sync returned 0) or exchange replay (dk_replay_exchange_finish, then dk_replay_sync
+ * returned 0), with dk_replay_scan_open's contract for compact, batch_rows, window_rows, leaves,
+ * lifetime and overflow; it is consumed with dk_scan_next / dk_scan_stats / dk_scan_close /
+ * dk_batch_release. It emits only this rank's own rows:
+ *   - the checkpoint rows it decoded (its row-group runs), one source per local checkpoint file;
+ *   - owner mode: the rows of the commit files (and JSON manifest parts) its dk_json_tail parsed;
+ *   - exchange mode: the (replicated) commit tail only when emit_tail, which exactly one rank of the
+ *     scan sets (two ranks setting it emit the tail's rows twice).
+ * A tail batch never spans two commit files: every parsed file is a source of its own, and
+ * dk_batch.row_index counts rows within that file. dk_batch.file is -1 / -2 / the LOCAL checkpoint
+ * file index as before.
+ * Refused, before anything is launched: a replay that is neither in owner nor in exchange mode; one
+ * whose protocol has not finished; opt == NULL; n_ckpt_files other than the replay's checkpoint
+ * files; n_tail_files other than the parsed tail files (owner mode) or 0 (exchange mode); a negative
+ * index. */
+typedef struct dk_rank_scan_options {
+  int32_t compact, batch_rows, window_rows;   /* as dk_scan_options */
+  int32_t emit_tail;           /* exchange mode: 1 on the one rank that emits the commit tail */
+  int32_t n_ckpt_files;        /* length of ckpt_index                                          */
+  int32_t n_tail_files;        /* length of tail_index                                          */
+  const int32_t* ckpt_index;   /* per local checkpoint file: its replay-order index in the whole scan */
+  const int32_t* tail_index;   /* owner mode, per parsed tail file: its replay-order index among the
+                                  scan's commit files (newest first), JSON manifest parts after them */
+} dk_rank_scan_options;
+int  dk_replay_scan_open_rank(dk_replay* r, const char* const* leaves, int32_t n_leaves,
+                              const dk_rank_scan_options* opt, dk_scan_reader** out);
+/* The order key of a rank reader's batch: out[0] = source class (0 commit tail, 1 JSON-manifest rows,
+ * 2 checkpoint file), out[1] = the source's replay-order index in the whole scan, out[2] = the source
+ * row of the batch's first row -- for a checkpoint file the FILE row, dk_parquet_row_offset + the row
+ * within the rank's row-group run, so that ranks holding different row groups of one part order
+ * correctly. Keys compare lexicographically; that order over all ranks' batches is Appendix B's.
+ * Fails for a batch that did not come from a rank reader. */
+int  dk_scan_batch_order(const dk_batch* b, int64_t out[3]);
+/* *selection = the batch's selection bytes (compact = 0; valid as long as the batch), NULL when the
+ * reader compacts: what dk_scan_next returned beside a batch that came out of a merge. */
+int  dk_scan_batch_selection(const dk_batch* b, const uint8_t** selection);
+/* One ordered iterator over the rank readers of one scan held by ONE process (the in-process world of
+ * dk_comm_create_local). dk_scan_merge_next yields the ranks' batches in order-key order (*out = NULL
+ * once every reader is exhausted; *rank = index into `readers` of the batch's origin), pulling from
+ * each reader only when its batch is needed: at most one batch per reader is looked ahead. The merge is
+ * at batch granularity: a rank's rows of a checkpoint file are one contiguous run of file rows, so
+ * batches never interleave row by row. That is checked: two readers whose rows of one checkpoint file
+ * overlap in file rows fail dk_scan_merge_open (nothing is launched), and a checkpoint batch that
+ * does not lie after the one before it fails dk_scan_merge_next. Equal tail keys (emit_tail on two
+ * ranks) come out in reader order. The merge uses the readers but does not own them: the caller closes
+ * them, before or after dk_scan_merge_close (after a reader is closed dk_scan_merge_next fails);
+ * closing the merge early is safe, and batches stay valid after both closes, until dk_batch_release.
+ * Single-threaded, like the readers: from dk_scan_merge_open to dk_scan_merge_close only the merge
+ * calls dk_scan_next on them. */
+typedef struct dk_scan_merge dk_scan_merge;
+int  dk_scan_merge_open(dk_scan_reader* const* readers, int32_t n, dk_scan_merge** out);
+int  dk_scan_merge_next(dk_scan_merge* m, dk_batch** out, int32_t* rank);
+void dk_scan_merge_close(dk_scan_merge* m);
+/* The reference's five ScanMetrics counters of a sharded scan from its ranks' finished replays: owner
+ * replays sum both halves over the ranks; exchange replays take the (replicated) commit-tail half
+ * from replays[0] and sum the checkpoint halves. All replays must be in the same mode. */
+int  dk_replay_counters_sum(dk_replay* const* replays, int32_t n, int64_t out[5]);
 
 /* ---- Data-row batches: Scan.transformPhysicalData with the predicate evaluated on the device
  * (KA/Scan.java:147-230; ExpressionHandler.getPredicateEvaluator(schema, predicate).eval(batch,
