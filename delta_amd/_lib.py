@@ -312,6 +312,63 @@ def check(rc):
         raise DkError(lib().dk_last_error().decode("utf-8", "replace"))
 
 
+class Handle:
+    """Owner of one native handle, `_h`: freed once, by close(), the end of a `with` block or garbage
+    collection, whichever comes first; None afterwards. A subclass names the export that frees it
+    (`_free_fn`) or overrides _free(h)."""
+    _h = None
+    _free_fn = None
+
+    def _open(self, fn, *args):
+        """Call a library constructor whose last argument receives the new handle."""
+        self._h = C.c_void_p()
+        check(fn(*args, C.byref(self._h)))
+
+    def _free(self, h):
+        getattr(lib(), self._free_fn)(h)
+
+    def close(self):
+        h, self._h = self._h, None
+        if h:
+            self._free(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                    # noqa: BLE001 -- interpreter shutdown
+            pass
+
+
+class BatchReader(Handle):
+    """A handle that hands out the library's dk_batch blocks. A subclass gives next_raw() -- None at
+    the end, else the dk_batch pointer, or a tuple that starts with it -- and batch(*raw), the Python
+    copy of one; iterating yields those copies and releases each block. close() early is safe, and
+    the copies stay valid after it."""
+
+    @staticmethod
+    def release(raw):
+        lib().dk_batch_release(raw)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        got = self.next_raw()
+        if got is None:
+            raise StopIteration
+        got = got if isinstance(got, tuple) else (got,)
+        try:
+            return self.batch(*got)
+        finally:
+            self.release(got[0])
+
+
 def _arr(ptr, n, dtype):
     if not ptr or n <= 0:
         return np.zeros(0, dtype=dtype)

@@ -20,7 +20,7 @@ from decimal import Decimal
 
 import numpy as np
 
-from ._lib import check, dk_parsed_column, lib
+from ._lib import Handle, check, dk_parsed_column, lib
 
 TYPES = ["long", "integer", "short", "byte", "date", "string", "timestamp", "decimal", "timestamp_ntz",
          "float", "double"]
@@ -49,9 +49,10 @@ def _json_text(x):
     return x if isinstance(x, str) else json.dumps(x)
 
 
-class ParsedBatch:
+class ParsedBatch(Handle):
     """JsonHandler.parseJson's ColumnarBatch: one row per input string (null where unselected or
     null), one typed column per leaf of the output schema, in schema order."""
+    _free_fn = "dk_parsed_free"
 
     def __init__(self, handle, n):
         self._h = handle
@@ -115,17 +116,6 @@ class ParsedBatch:
             else:
                 out.append(int(c["values"][r]))
         return out
-
-    def close(self):
-        if self._h:
-            lib().dk_parsed_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class GpuJsonHandler:

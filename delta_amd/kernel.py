@@ -20,14 +20,16 @@ import ctypes as C
 import json
 import os
 import re
+import threading
 import time
 import weakref
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (MAX_LEAF_DEPTH, Column, DkError, check, dk_batch, dk_column, dk_config, dk_data_options,
-                   dk_dv_descriptor, dk_rank_scan_options, dk_read_options, dk_rg_filter, dk_scan_options, lib)
+from ._lib import (MAX_LEAF_DEPTH, BatchReader, Column, DkError, Handle, check, dk_batch, dk_column, dk_config,
+                   dk_data_options, dk_dv_descriptor, dk_rank_scan_options, dk_read_options, dk_rg_filter,
+                   dk_scan_options, lib)
 
 ADD_LEAVES = ["add.path", "add.partitionValues.key_value.key", "add.partitionValues.key_value.value",
               "add.size", "add.modificationTime", "add.dataChange",
@@ -53,6 +55,11 @@ DOMAIN_LEAVES = ["domainMetadata.domain", "domainMetadata.configuration", "domai
 TIMING = 1
 
 
+def scan_leaves(read_stats):
+    """The leaves of a scan file: the add action's, with add.stats when the scan reads statistics."""
+    return ADD_LEAVES + ([STATS_LEAF] if read_stats else [])
+
+
 def scan_groups(n_files):
     """Groups of checkpoint files for a grouped getScanFiles run (dk_replay_run_grouped): about 8
     files per group, at most 8 groups; DK_SCAN_GROUPS overrides (0: one ungrouped run)."""
@@ -68,30 +75,19 @@ def _cstrs(items):
     return arr
 
 
-class GpuEngine:
+class GpuEngine(Handle):
     """Engine (engine/Engine.java:30-64) backed by one MI355X."""
+    _free_fn = "dk_engine_destroy"
 
     def __init__(self, parquet_batch_size=1024, json_batch_size=1024, device=0, timing=False):
         self.cfg = dk_config(parquet_batch_size, json_batch_size, device, TIMING if timing else 0)
-        self._h = C.c_void_p()
-        check(lib().dk_engine_create(C.byref(self.cfg), C.byref(self._h)))
+        self._open(lib().dk_engine_create, C.byref(self.cfg))
 
     create = classmethod(lambda cls, **kw: cls(**kw))
 
     @property
     def json_batch_size(self):
         return self.cfg.json_batch_size
-
-    def close(self):
-        if self._h:
-            lib().dk_engine_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ParquetHandler.readParquetFiles (engine/ParquetHandler.java:64-68)
     def read_parquet_files(self, paths, leaves):
@@ -106,41 +102,47 @@ class GpuEngine:
         return ParquetReader(self, paths, leaves, predicate, field_ids, window_rows)
 
 
-def prune_row_groups(path, packed_filter):
-    """Row groups of `path` that survive the checkpoint predicate (dk_parquet_prune_row_groups)."""
+def _row_group_query(path, ctype, call):
+    """One `ctype` value per row group of `path`, from a footer-only query: call(out, cap, n) fills
+    out[:cap] and sets n to the file's row-group count."""
     cap = 4096
-    keep = (C.c_uint8 * cap)()
-    n = C.c_int32()
-    check(lib().dk_parquet_prune_row_groups(path.encode(), C.byref(packed_filter), keep, cap, C.byref(n)))
+    out, n = (ctype * cap)(), C.c_int32()
+    check(call(out, cap, C.byref(n)))
     if n.value > cap:
         raise DkError("%s has more than %d row groups" % (path, cap))
-    return [g for g in range(n.value) if keep[g]]
+    return out[:n.value]
+
+
+def prune_row_groups(path, packed_filter):
+    """Row groups of `path` that survive the checkpoint predicate (dk_parquet_prune_row_groups)."""
+    keep = _row_group_query(path, C.c_uint8, lambda *out: lib().dk_parquet_prune_row_groups(
+        path.encode(), C.byref(packed_filter), *out))
+    return [g for g, k in enumerate(keep) if k]
 
 
 def nonnull_row_groups(path, leaf):
     """keep flag per row group: False where footer statistics show `leaf` null in every row."""
-    cap = 4096
-    keep = (C.c_uint8 * cap)()
-    n = C.c_int32()
-    check(lib().dk_parquet_nonnull_row_groups(path.encode(), leaf.encode(), keep, cap, C.byref(n)))
-    if n.value > cap:
-        raise DkError("%s has more than %d row groups" % (path, cap))
-    return [bool(keep[g]) for g in range(n.value)]
+    return [bool(k) for k in _row_group_query(path, C.c_uint8, lambda *out: lib().dk_parquet_nonnull_row_groups(
+        path.encode(), leaf.encode(), *out))]
 
 
 def row_group_rows(path):
     """Row counts of a Parquet file's row groups (footer only)."""
-    cap = 4096
-    rows = (C.c_int64 * cap)()
-    n = C.c_int32()
-    check(lib().dk_parquet_row_groups(path.encode(), rows, cap, C.byref(n)))
-    if n.value > cap:
-        raise DkError("%s has more than %d row groups" % (path, cap))
-    return [int(rows[i]) for i in range(n.value)]
+    return _row_group_query(path, C.c_int64, lambda *out: lib().dk_parquet_row_groups(path.encode(), *out))
 
 
-class ParquetSet:
+def _int32s(values):
+    return (C.c_int32 * max(1, len(values)))(*values)
+
+
+def _row_group_lists(groups):
+    """Row-group indices per file as the library takes them: (count per file, the indices end to end)."""
+    return _int32s([len(g) for g in groups]), _int32s([g for gs in groups for g in gs])
+
+
+class ParquetSet(Handle):
     """A set of Parquet files decoded on the GPU (one batch per file; batches in input order)."""
+    _free_fn = "dk_parquet_close"
 
     def __init__(self, engine: GpuEngine, paths, leaves, row_groups=None, groups=None, async_open=False):
         """row_groups: optional [(first, end)] row-group range per file (dk_parquet_open_rg);
@@ -150,30 +152,18 @@ class ParquetSet:
         self.engine = engine
         self.paths = list(paths)
         self.leaves = list(leaves)
-        self._h = C.c_void_p()
         self.async_open = bool(async_open and row_groups is None)
-        if async_open and row_groups is None:
-            cnt = lst = None
-            if groups is not None:
-                cnt = (C.c_int32 * max(1, len(groups)))(*[len(g) for g in groups])
-                flat = [g for gs in groups for g in gs]
-                lst = (C.c_int32 * max(1, len(flat)))(*flat)
-            check(lib().dk_parquet_open_async(engine._h, _cstrs(self.paths), len(self.paths), _cstrs(self.leaves),
-                                              len(self.leaves), cnt, lst, C.byref(self._h)))
+        files = (engine._h, _cstrs(self.paths), len(self.paths), _cstrs(self.leaves), len(self.leaves))
+        if self.async_open:
+            cnt, lst = _row_group_lists(groups) if groups is not None else (None, None)
+            self._open(lib().dk_parquet_open_async, *files, cnt, lst)
         elif groups is not None:
-            cnt = (C.c_int32 * max(1, len(groups)))(*[len(g) for g in groups])
-            flat = [g for gs in groups for g in gs]
-            lst = (C.c_int32 * max(1, len(flat)))(*flat)
-            check(lib().dk_parquet_open_sel(engine._h, _cstrs(self.paths), len(self.paths), _cstrs(self.leaves),
-                                            len(self.leaves), cnt, lst, C.byref(self._h)))
+            self._open(lib().dk_parquet_open_sel, *files, *_row_group_lists(groups))
         elif row_groups is None:
-            check(lib().dk_parquet_open(engine._h, _cstrs(self.paths), len(self.paths), _cstrs(self.leaves),
-                                        len(self.leaves), C.byref(self._h)))
+            self._open(lib().dk_parquet_open, *files)
         else:
-            lo = (C.c_int32 * max(1, len(row_groups)))(*[a for a, _ in row_groups])
-            hi = (C.c_int32 * max(1, len(row_groups)))(*[b for _, b in row_groups])
-            check(lib().dk_parquet_open_rg(engine._h, _cstrs(self.paths), len(self.paths), _cstrs(self.leaves),
-                                           len(self.leaves), lo, hi, C.byref(self._h)))
+            self._open(lib().dk_parquet_open_rg, *files, _int32s([a for a, _ in row_groups]),
+                       _int32s([b for _, b in row_groups]))
 
     def decode(self):
         check(lib().dk_parquet_decode(self._h))
@@ -253,17 +243,6 @@ class ParquetSet:
         check(lib().dk_parquet_kernel_traffic(self._h, kernel.encode(), C.byref(r), C.byref(w)))
         return r.value, w.value
 
-    def close(self):
-        if self._h:
-            lib().dk_parquet_close(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 ROW_INDEX_COLUMN = "_metadata.row_index"     # StructField.METADATA_ROW_INDEX_COLUMN_NAME
 
@@ -316,29 +295,35 @@ class ColumnarBatch:
         self.row_index = _np_view(b.row_index, b.n_rows, np.int64).copy() if want_row_index else None
 
 
-class ParquetReader:
+def field_id_matrix(leaves, field_ids):
+    """The readers' field_ids option: MAX_LEAF_DEPTH int32 per leaf (at least one leaf's worth), the
+    parquet.field.id of each dotted component of the leaf; -1 where field_ids ({leaf: [id or None]})
+    gives none."""
+    ids = np.full(max(1, len(leaves)) * MAX_LEAF_DEPTH, -1, np.int32)
+    for i, leaf in enumerate(leaves):
+        for d, v in enumerate((field_ids.get(leaf) or [])[:MAX_LEAF_DEPTH]):
+            ids[i * MAX_LEAF_DEPTH + d] = -1 if v is None else v
+    return ids
+
+
+class ParquetReader(BatchReader):
     """Iterator over dk_reader batches; close() early is safe (ScanImpl.java:376-392)."""
+    _free_fn = "dk_reader_close"
 
     def __init__(self, engine, paths, leaves, predicate=None, field_ids=None, window_rows=0):
         self.paths = list(paths)
         self.want_row_index = ROW_INDEX_COLUMN in leaves
         self.leaves = [x for x in leaves if x != ROW_INDEX_COLUMN]
         opt = dk_read_options()
-        self._ids = None
-        if field_ids:
-            ids = np.full(len(self.leaves) * MAX_LEAF_DEPTH, -1, np.int32)
-            for i, leaf in enumerate(self.leaves):
-                for d, v in enumerate((field_ids.get(leaf) or [])[:MAX_LEAF_DEPTH]):
-                    ids[i * MAX_LEAF_DEPTH + d] = -1 if v is None else v
-            self._ids = ids
-            opt.field_ids = ids.ctypes.data
+        self._ids = field_id_matrix(self.leaves, field_ids) if field_ids else None   # (alive while the handle is)
+        if self._ids is not None:
+            opt.field_ids = self._ids.ctypes.data
         self._pred = predicate
         opt.predicate = C.cast(C.byref(predicate), C.c_void_p) if predicate is not None else None
         opt.row_index = 1 if self.want_row_index else 0
         opt.window_rows = window_rows
-        self._h = C.c_void_p()
-        check(lib().dk_reader_open(engine._h, _cstrs(self.paths), len(self.paths), _cstrs(self.leaves),
-                                   len(self.leaves), C.byref(opt), C.byref(self._h)))
+        self._open(lib().dk_reader_open, engine._h, _cstrs(self.paths), len(self.paths), _cstrs(self.leaves),
+                   len(self.leaves), C.byref(opt))
 
     def num_rows(self, file_idx):
         return lib().dk_reader_num_rows(self._h, file_idx)
@@ -349,44 +334,15 @@ class ParquetReader:
         check(lib().dk_reader_next(self._h, C.byref(out)))
         return out if out else None
 
-    @staticmethod
-    def release(raw):
-        lib().dk_batch_release(raw)
-
-    def __iter__(self):
-        return self
-
-    def __next__(self):
-        raw = self.next_raw()
-        if raw is None:
-            raise StopIteration
-        try:
-            return ColumnarBatch(raw.contents, self.leaves, self.want_row_index)
-        finally:
-            lib().dk_batch_release(raw)
-
-    def close(self):
-        if self._h:
-            lib().dk_reader_close(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def batch(self, raw):
+        return ColumnarBatch(raw.contents, self.leaves, self.want_row_index)
 
 
-class DeletionVectors:
+class DeletionVectors(Handle):
     """The DVs of a set of scan files, loaded into dense deleted-row bitmaps on the GPU
     (DeletionVectorUtils.loadNewDvAndBitmap, DeletionVectorUtils.java:27-37). descriptors: tuples
     (storageType, pathOrInlineDv, offset or None, sizeInBytes, cardinality)."""
+    _free_fn = "dk_dv_free"
 
     def __init__(self, engine, table_root, descriptors):
         self.n = len(descriptors)
@@ -399,8 +355,7 @@ class DeletionVectors:
             arr[i].has_offset = 0 if off is None else 1
             arr[i].offset = off or 0
             arr[i].size_in_bytes, arr[i].cardinality = size, card
-        self._h = C.c_void_p()
-        check(lib().dk_dv_load(engine._h, table_root.encode(), arr, self.n, C.byref(self._h)))
+        self._open(lib().dk_dv_load, engine._h, table_root.encode(), arr, self.n)
 
     def num_bits(self, i):
         return lib().dk_dv_num_bits(self._h, i)
@@ -419,17 +374,6 @@ class DeletionVectors:
         check(lib().dk_dv_selection(self._h, i, ri.ctypes.data, ri.size, sel.ctypes.data))
         return sel[:ri.size].astype(bool)
 
-    def close(self):
-        if self._h:
-            lib().dk_dv_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _dv_of(data, r):
     """(storageType, pathOrInlineDv, offset, sizeInBytes, cardinality) of scan-file row r, or None."""
@@ -444,24 +388,34 @@ def _dv_of(data, r):
             int(off.fixed.view("<i4")[r]) if has_off else None, int(size), int(card))
 
 
+def data_file_path(table_root, add_path):
+    """The local path of a scan file's data file: add.path is a URI, relative to tableRoot (and then
+    percent-encoded) unless it names a scheme; a `file:` prefix is dropped."""
+    from urllib.parse import unquote
+    full = add_path if re.match(r"^[A-Za-z][A-Za-z0-9+.-]*:", add_path) else \
+        table_root.rstrip("/") + "/" + unquote(add_path)
+    return full[5:] if full.startswith("file:") else full
+
+
+def selected_scan_files(scan, engine):
+    """(add.path, deletion vector as _dv_of gives it, partition values) of every selected scan file
+    of scan.getScanFiles, in its order."""
+    return [(b.data["add.path"].string(r).decode(), _dv_of(b.data, r), _partition_values_of(b.data, r))
+            for b in scan.getScanFiles(engine) for r in map(int, b.selected_rows())]
+
+
 def read_scan_data(engine, scan, leaves):
     """Scan.transformPhysicalData over every selected scan file (Scan.java:147-230): each data file
     is read with the row-index metadata column (readParquetFiles) and, when the scan file carries a
     deletion vector, filtered by it (SelectionColumnVector). Yields (add.path, ColumnarBatch,
     selection or None)."""
-    from urllib.parse import unquote
     root = scan.table_root()
-    files = []
-    for b in scan.getScanFiles(engine):
-        for r in b.selected_rows():
-            files.append((b.data["add.path"].string(int(r)).decode(), _dv_of(b.data, int(r))))
-    with_dv = [dv for _, dv in files if dv is not None]
+    files = selected_scan_files(scan, engine)
+    with_dv = [dv for _, dv, _ in files if dv is not None]
     dvs = DeletionVectors(engine, root, with_dv) if with_dv else None
     k = 0
-    for path, dv in files:
-        full = path if re.match(r"^[A-Za-z][A-Za-z0-9+.-]*:", path) else root.rstrip("/") + "/" + unquote(path)
-        local = full[5:] if full.startswith("file:") else full
-        with engine.readParquetFiles([local], list(leaves) + [ROW_INDEX_COLUMN]) as rd:
+    for path, dv, _ in files:
+        with engine.readParquetFiles([data_file_path(root, path)], list(leaves) + [ROW_INDEX_COLUMN]) as rd:
             for batch in rd:
                 sel = dvs.selection(k, batch.row_index) if dv is not None else None
                 yield path, batch, sel
@@ -489,7 +443,25 @@ class DataBatch:
         return len(self.row_index)
 
 
-class DataReader:
+class _ScanReader(BatchReader):
+    """A reader of the library's dk_scan_reader kind (DataReader, ScanFileReader): batches through
+    dk_scan_next, each with its selection bytes."""
+    _free_fn = "dk_scan_close"
+
+    def next_raw(self):
+        """(dk_batch pointer, selection address or None), or None at the end."""
+        out, sel = C.POINTER(dk_batch)(), C.c_void_p()
+        check(lib().dk_scan_next(self._h, C.byref(out), C.byref(sel)))
+        return (out, sel.value) if out else None
+
+    def stats(self):
+        """bytes copied from the device, windows loaded, rows and batches emitted so far."""
+        st = (C.c_int64 * 4)()
+        check(lib().dk_scan_stats(self._h, st))
+        return dict(d2h_bytes=int(st[0]), windows=int(st[1]), rows=int(st[2]), batches=int(st[3]))
+
+
+class DataReader(_ScanReader):
     """dk_data_scan_open over data files: deletion vectors and a compiled data filter
     (programs.compile_data_filter) applied per row on the device, batches through dk_scan_next.
     dvs: a DeletionVectors set with dv_index[f] = file f's DV in it (-1: none); predicate: a packed
@@ -500,12 +472,9 @@ class DataReader:
         self.paths = list(paths)
         self.leaves = list(leaves)
         opt = dk_data_options()
-        self._keep = [filter, dvs, predicate]
+        self._keep = [filter, dvs, predicate]       # what the library reads for as long as the handle lives
         if field_ids:
-            ids = np.full(max(1, len(self.leaves)) * MAX_LEAF_DEPTH, -1, np.int32)
-            for i, leaf in enumerate(self.leaves):
-                for d, v in enumerate((field_ids.get(leaf) or [])[:MAX_LEAF_DEPTH]):
-                    ids[i * MAX_LEAF_DEPTH + d] = -1 if v is None else v
+            ids = field_id_matrix(self.leaves, field_ids)
             self._keep.append(ids)
             opt.field_ids = ids.ctypes.data
         opt.predicate = C.cast(C.byref(predicate), C.c_void_p) if predicate is not None else None
@@ -518,25 +487,8 @@ class DataReader:
             opt.dv_index = dvi.ctypes.data if dvi.size else None
         opt.filter = filter.handle if filter is not None else None
         opt.compact, opt.batch_rows, opt.window_rows = (1 if compact else 0), int(batch_rows or 0), int(window_rows or 0)
-        self._h = C.c_void_p()
-        check(lib().dk_data_scan_open(engine._h, _cstrs(self.paths), len(self.paths), _cstrs(self.leaves),
-                                      len(self.leaves), C.byref(opt), C.byref(self._h)))
-
-    def next_raw(self):
-        """(dk_batch pointer, selection address or None), or None at the end."""
-        out, sel = C.POINTER(dk_batch)(), C.c_void_p()
-        check(lib().dk_scan_next(self._h, C.byref(out), C.byref(sel)))
-        return (out, sel.value) if out else None
-
-    @staticmethod
-    def release(raw):
-        lib().dk_batch_release(raw)
-
-    def stats(self):
-        """bytes copied from the device, windows loaded, rows and batches emitted so far."""
-        st = (C.c_int64 * 4)()
-        check(lib().dk_scan_stats(self._h, st))
-        return dict(d2h_bytes=int(st[0]), windows=int(st[1]), rows=int(st[2]), batches=int(st[3]))
+        self._open(lib().dk_data_scan_open, engine._h, _cstrs(self.paths), len(self.paths), _cstrs(self.leaves),
+                   len(self.leaves), C.byref(opt))
 
     def batch(self, raw, sel):
         b = raw.contents
@@ -545,35 +497,6 @@ class DataReader:
                          {leaf: BatchColumn(b.cols[i], n, leaf) for i, leaf in enumerate(self.leaves)},
                          _np_view(sel, n, np.uint8).astype(bool) if sel else None,
                          _np_view(b.row_index, n, np.int64).copy())
-
-    def __iter__(self):
-        return self
-
-    def __next__(self):
-        got = self.next_raw()
-        if got is None:
-            raise StopIteration
-        try:
-            return self.batch(*got)
-        finally:
-            lib().dk_batch_release(got[0])
-
-    def close(self):
-        if self._h:
-            lib().dk_scan_close(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _physical_predicate(pred, logical, physical):
@@ -636,18 +559,18 @@ def _partition_values_of(data, r):
     return out
 
 
-class JsonTail:
+class JsonTail(Handle):
     """Commit files parsed on the host (DefaultJsonHandler.readJsonFiles semantics), optionally
     followed by JSON-format checkpoint parts (a V2 checkpoint's JSON manifest): rows
     [ckpt_row0, rows) are those parts' rows, whose adds reconcile as checkpoint adds."""
+    _free_fn = "dk_json_tail_free"
 
     def __init__(self, engine: GpuEngine, commit_paths, versions, with_stats=False, checkpoint_paths=()):
-        self._h = C.c_void_p()
         paths = list(commit_paths) + list(checkpoint_paths)
         versions = list(versions) + [0] * len(checkpoint_paths)
         vers = (C.c_int64 * max(1, len(versions)))(*versions)
-        check(lib().dk_json_tail_parse_parts(engine._h, _cstrs(paths), vers, len(paths), len(checkpoint_paths),
-                                             1 if with_stats else 0, C.byref(self._h)))
+        self._open(lib().dk_json_tail_parse_parts, engine._h, _cstrs(paths), vers, len(paths), len(checkpoint_paths),
+                   1 if with_stats else 0)
         self.rows = lib().dk_json_tail_rows(self._h)
         self.ckpt_row0 = lib().dk_json_tail_checkpoint_row0(self._h)
 
@@ -655,17 +578,6 @@ class JsonTail:
         c = dk_column()
         check(lib().dk_json_tail_column(self._h, leaf.encode(), C.byref(c)))
         return Column(c, leaf)
-
-    def close(self):
-        if self._h:
-            lib().dk_json_tail_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1322,6 +1234,9 @@ class ScanBuilder:
         self.read_stats = False
         self.shard = None
         self.predicate = None
+        self.read_schema = None
+        self.exchange = None
+        self.owner = None
 
     def withFilter(self, predicate):
         """ScanBuilderImpl.withFilter (internal/ScanBuilderImpl.java:61-67). The partition part of the
@@ -1359,12 +1274,8 @@ class ScanBuilder:
         return self
 
     def build(self):
-        sc = GpuScan(self.snapshot, self.read_stats, self.shard, self.predicate)
-        sc.read_schema = getattr(self, "read_schema", None)
-        sc.exchange = getattr(self, "exchange", None)
-        # owner mode: an explicit owner communicator (also at world 1: one RCCL rank through the ABI)
-        sc.owner = getattr(self, "owner", None) if self.shard else None
-        return sc
+        return GpuScan(self.snapshot, self.read_stats, self.shard, self.predicate, read_schema=self.read_schema,
+                       exchange=self.exchange, owner=self.owner)
 
 
 def _own_column(c):
@@ -1418,8 +1329,17 @@ class LazyColumns(dict):
         return [self[k] for k in self._leaves]
 
 
+class _Selected:
+    """selected_rows() of a batch with a `size` and a `selection` (None: every row)."""
+
+    def selected_rows(self):
+        if self.selection is None:
+            return np.arange(self.size)
+        return np.nonzero(self.selection)[0]
+
+
 @dataclass
-class FilteredColumnarBatch:
+class FilteredColumnarBatch(_Selected):
     """data: leaf -> Column (add.* leaves) plus the constant tableRoot; selection: bool per row or
     None when every row is selected (KA/data/FilteredColumnarBatch.java:37-111)."""
     data: dict
@@ -1431,14 +1351,9 @@ class FilteredColumnarBatch:
     row_offset: int = 0           # file row of this batch's first row (row-group shards)
     commit_index: int = -1        # owner mode: the commit file's replay-order index (tail batches)
 
-    def selected_rows(self):
-        if self.selection is None:
-            return np.arange(self.size)
-        return np.nonzero(self.selection)[0]
-
 
 @dataclass
-class ScanFileBatch:
+class ScanFileBatch(_Selected):
     """One batch of GpuScan.getScanFileBatches: at most batch_rows scan-file rows of one source in
     the ParquetHandler reader's layout (BatchColumn: validity bits, int32 offsets). selection: bool
     per row, or None in compact mode (every row of the batch is selected); row_index: the source row
@@ -1459,13 +1374,8 @@ class ScanFileBatch:
     order: tuple | None = None
     rank: int = -1
 
-    def selected_rows(self):
-        if self.selection is None:
-            return np.arange(self.size)
-        return np.nonzero(self.selection)[0]
 
-
-class ScanFileReader:
+class ScanFileReader(_ScanReader):
     """dk_scan_reader over a scan's finished replay (dk_replay_scan_open): next_raw() hands out the
     library's dk_batch (released with release()), iterating yields ScanFileBatch copies. close()
     early is safe; batches stay valid after it.
@@ -1482,40 +1392,19 @@ class ScanFileReader:
 
     def __init__(self, scan, compact=True, batch_rows=None, window_rows=0, leaves=None, emit_tail=None):
         self.scan = scan
-        self.leaves = list(leaves) if leaves is not None else ADD_LEAVES + ([STATS_LEAF] if scan.read_stats else [])
-        self._h = C.c_void_p()
-        owner = getattr(scan, "owner", None)
-        self.rank_reader = owner is not None or \
-            (getattr(scan, "exchange", None) is not None and bool(scan.shard) and scan.shard[0] > 1)
+        self.leaves = list(leaves) if leaves is not None else scan_leaves(scan.read_stats)
+        self.rank_reader = scan.exchanging
         if self.rank_reader:
             ck = [int(i) for i in (scan.ckpt_index if scan.ckpt is not None else [])]
-            tf = [int(j) for j in scan.tail_commits + scan.tail_parts] if owner is not None else []
-            self._keep = ((C.c_int32 * max(1, len(ck)))(*ck), (C.c_int32 * max(1, len(tf)))(*tf))
+            tf = [int(j) for j in scan.tail_commits + scan.tail_parts] if scan.owner is not None else []
+            self._keep = (_int32s(ck), _int32s(tf))     # the library reads them for as long as the handle lives
             emit = scan.shard[1] == 0 if emit_tail is None else bool(emit_tail)
             ropt = dk_rank_scan_options(1 if compact else 0, int(batch_rows or 0), int(window_rows or 0), int(emit),
                                         len(ck), len(tf), self._keep[0], self._keep[1])
-            check(lib().dk_replay_scan_open_rank(scan._rh, _cstrs(self.leaves), len(self.leaves), C.byref(ropt),
-                                                 C.byref(self._h)))
+            self._open(lib().dk_replay_scan_open_rank, scan._rh, _cstrs(self.leaves), len(self.leaves), C.byref(ropt))
             return
         opt = dk_scan_options(1 if compact else 0, int(batch_rows or 0), int(window_rows or 0))
-        check(lib().dk_replay_scan_open(scan._rh, _cstrs(self.leaves), len(self.leaves), C.byref(opt),
-                                        C.byref(self._h)))
-
-    def next_raw(self):
-        """(dk_batch pointer, selection address or None), or None at the end."""
-        out, sel = C.POINTER(dk_batch)(), C.c_void_p()
-        check(lib().dk_scan_next(self._h, C.byref(out), C.byref(sel)))
-        return (out, sel.value) if out else None
-
-    @staticmethod
-    def release(raw):
-        lib().dk_batch_release(raw)
-
-    def stats(self):
-        """bytes copied from the device, windows loaded, rows and batches emitted so far."""
-        st = (C.c_int64 * 4)()
-        check(lib().dk_scan_stats(self._h, st))
-        return dict(d2h_bytes=int(st[0]), windows=int(st[1]), rows=int(st[2]), batches=int(st[3]))
+        self._open(lib().dk_replay_scan_open, scan._rh, _cstrs(self.leaves), len(self.leaves), C.byref(opt))
 
     def batch(self, raw, sel):
         b = raw.contents
@@ -1537,28 +1426,86 @@ class ScanFileReader:
                              _np_view(sel, n, np.uint8).astype(bool) if sel else None,
                              _np_view(b.row_index, n, np.int64).copy(), fidx, source, order)
 
-    def __iter__(self):
-        return self
 
-    def __next__(self):
-        got = self.next_raw()
-        if got is None:
-            raise StopIteration
+class _TailParse:
+    """The commit-tail half of GpuScan.prepare, on a thread of its own beside the checkpoint open:
+    the JsonTail of this rank's commit files (and JSON manifest parts), in owner mode the vote that
+    makes their batch counts global, then the replay's commit-tail half (action table + key-table
+    inputs). Results: tail, rh (the dk_replay handle), ms / create_ms (parse and replay-create
+    times); error: what the thread raised, for the calling thread to raise."""
+    NOT_VOTED, VOTE_FAILED, VOTE_PASSED = range(3)
+
+    def __init__(self, scan, engine, commits, parts, n_files_all):
+        self.scan, self.engine, self.commits, self.parts = scan, engine, commits, parts
+        self.owner = scan.owner
+        self.no_steps = np.zeros(n_files_all, np.int64)     # batches per commit file of the whole scan: none
+        self.tail = self.rh = self.error = self.ms = self.create_ms = None
+        self.vote = self.NOT_VOTED
+        self.started = False
+        self._thread = threading.Thread(target=self._run, daemon=True)
+
+    def start(self):
+        if not self.started:
+            self.started = True
+            self._thread.start()
+
+    def join(self):
+        self._thread.join()
+
+    def _run(self):
         try:
-            return self.batch(*got)
-        finally:
-            lib().dk_batch_release(got[0])
+            self._parse()
+        except BaseException as e:          # re-raised on the calling thread
+            self.error = e
 
-    def close(self):
-        if self._h:
-            lib().dk_scan_close(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
+    def _parse(self):
+        scan, owner = self.scan, self.owner
+        t = time.perf_counter()
         try:
-            self.close()
-        except Exception:
-            pass
+            tail = JsonTail(self.engine, [d.path for d in self.commits], [d.version for d in self.commits],
+                            scan.read_stats, checkpoint_paths=self.parts)
+        except BaseException:
+            if owner is not None:
+                # the peers wait in global_steps: this rank's one call tells them, and they raise with it
+                self.vote = self.VOTE_FAILED
+                owner.global_steps(self.no_steps, failed=True)
+            raise
+        self.tail = tail
+        if owner is not None:
+            files = scan.tail_commits + scan.tail_parts
+            steps = _int32s([0] * len(files))
+            check(lib().dk_json_tail_file_steps(tail._h, steps))
+            local = self.no_steps.copy()
+            for k, j in enumerate(files):
+                local[j] = steps[k]
+            self.vote = self.VOTE_FAILED        # this rank's one call to global_steps: failed unless it returns
+            total = np.asarray(owner.global_steps(local), dtype=np.int64)
+            self.vote = self.VOTE_PASSED
+            step0 = np.concatenate([[0], np.cumsum(total)])
+            if step0[-1] >= (1 << 31) - 1:
+                raise DkError("owner mode: more than 2^31 commit-tail batches")
+            check(lib().dk_json_tail_rebase_steps(tail._h, _int32s([int(step0[j]) for j in files])))
+            row0 = (C.c_int64 * (len(files) + 1))()
+            check(lib().dk_json_tail_file_row0(tail._h, row0))
+            scan.tail_file_rows = [(files[k], int(row0[k]), int(row0[k + 1])) for k in range(len(files))]
+        self.ms = (time.perf_counter() - t) * 1e3
+        t = time.perf_counter()
+        rh = C.c_void_p()
+        check(lib().dk_replay_create(self.engine._h, tail._h, None, C.byref(rh)))
+        self.rh = rh
+        self.create_ms = (time.perf_counter() - t) * 1e3
+
+    def fail_peers(self):
+        """This rank is about to raise from prepare: make sure its peers raise too instead of
+        waiting for it in a collective (global_steps, or the owner run's first vote)."""
+        if self.owner is None or self.vote == self.VOTE_FAILED:
+            return                          # a failed vote: every rank raised at global_steps, nothing more is sent
+        if self.vote == self.NOT_VOTED:
+            # failed before it could vote (or the parse never started): its one call to global_steps
+            self.vote = self.VOTE_FAILED
+            self.owner.global_steps(self.no_steps, failed=True)
+        else:
+            self.owner.abort()              # the vote passed: this rank answers the owner run's first vote
 
 
 class GpuScan:
@@ -1568,10 +1515,16 @@ class GpuScan:
     # leaves mirrored to host memory per decoded group (dk_replay_prefetch_leaf)
     PREFETCH_LEAVES = ("add.size",)
 
-    def __init__(self, snapshot, read_stats=False, shard=None, predicate=None):
+    def __init__(self, snapshot, read_stats=False, shard=None, predicate=None, *, read_schema=None, exchange=None,
+                 owner=None):
         self.snapshot = snapshot
         self.shard = shard
         self.predicate = predicate
+        self.read_schema = read_schema
+        self.exchange = exchange
+        # owner mode: an explicit owner communicator (also at world 1: one RCCL rank through the ABI),
+        # honoured only on a sharded scan
+        self.owner = owner if shard else None
         self.skipping = None          # (planner node, compiled Program) when a data-skipping filter applies
         self._deferred_error = None
         self.partition = None
@@ -1611,10 +1564,22 @@ class GpuScan:
         self.metrics = ScanMetrics()
         self.tail_metrics = ScanMetrics()
         self.ckpt_metrics = ScanMetrics()
-        self.replay = None
-        self.prepare_ms = {}
+        self.replay = None            # True once prepare() has run
+        self._synced = False          # the last run's results and counters are final (sync)
+        self.ckpt, self.tail, self._rh = None, None, None     # ParquetSet, JsonTail, dk_replay handle (prepare)
+        self.ckpt_files, self.ckpt_index = [], []   # this scan's checkpoint files; their replay-order indices
+        # owner mode: replay-order indices of the commit files and JSON manifest parts this rank
+        # parses, and (index, first row, end row) of each in its tail
+        self.tail_commits, self.tail_parts, self.tail_file_rows = [], [], []
+        self.prepare_ms, self.close_ms = {}, {}
         self._handed = weakref.WeakValueDictionary()   # zero-copy checkpoint batches handed out (_detach_batches)
         self._scan_readers = weakref.WeakSet()         # open ScanFileReaders (getScanFileBatches)
+
+    @property
+    def exchanging(self):
+        """This scan's run exchanges with peers, and its scan files stream per rank: an owner scan
+        (at any world size), or an exchange scan of more than one rank."""
+        return self.owner is not None or (self.exchange is not None and bool(self.shard) and self.shard[0] > 1)
 
     def table_root(self):
         """tableRoot = dataPath.toUri().toString() (ActiveAddFilesIterator.java:251)."""
@@ -1628,7 +1593,7 @@ class GpuScan:
         schemas as the reference's JSON text (delta_amd/schema.py)."""
         from . import schema
         return schema.scan_state(self.snapshot.metadata or {}, self.snapshot.protocol or {}, self.table_root(),
-                                 read_schema=getattr(self, "read_schema", None))
+                                 read_schema=self.read_schema)
 
     def prepare(self, engine):
         """Host-side setup: parse the commit tail, open checkpoint files, upload to HBM."""
@@ -1637,123 +1602,54 @@ class GpuScan:
         t0 = time.perf_counter()
         seg = self.snapshot.log_segment
         commits = list(reversed(seg.deltas))
-        # the commit tail is parsed (host threads, GIL released in the library) while the checkpoint
-        # files are opened below; its errors still surface first, as in the reference's replay order
-        import threading
-        tail_box = {}
-
-        owner = getattr(self, "owner", None)
         parts = self.snapshot._json_checkpoint_parts()
-        if owner is not None:
+        n_files_all = len(commits) + len(parts)
+        if self.owner is not None:
             # owner mode: this rank parses the commit files j = rank (mod world) of the replay order
             # (newest first) and, on rank 0, the JSON manifest; their batch steps are renumbered in
             # the global replay order once the ranks' batch counts are known (owner.global_steps)
             world, rank = self.shard
             self.tail_commits = [j for j in range(len(commits)) if j % world == rank]
-            self.tail_parts = list(range(len(commits), len(commits) + len(parts))) if rank == 0 else []
-            mine = [commits[j] for j in self.tail_commits]
+            self.tail_parts = list(range(len(commits), n_files_all)) if rank == 0 else []
+            commits = [commits[j] for j in self.tail_commits]
             parts = parts if rank == 0 else []
-        else:
-            mine = commits
-
-        n_files_all = len(commits) + len(self.snapshot._json_checkpoint_parts())
-
-        def parse_tail():
-            # the tail, then the replay's commit-tail half (action table + key-table inputs)
-            t = time.perf_counter()
-            try:
-                try:
-                    tail = JsonTail(engine, [d.path for d in mine], [d.version for d in mine], self.read_stats,
-                                    checkpoint_paths=parts)
-                except BaseException:
-                    if owner is not None:   # the peers wait in global_steps: they raise with this rank
-                        tail_box["voted"] = "failed"
-                        owner.global_steps(np.zeros(n_files_all, np.int64), failed=True)
-                    raise
-                tail_box["tail"] = tail
-                if owner is not None:
-                    files = self.tail_commits + self.tail_parts
-                    steps = (C.c_int32 * max(1, len(files)))()
-                    check(lib().dk_json_tail_file_steps(tail._h, steps))
-                    local = np.zeros(n_files_all, np.int64)
-                    for k, j in enumerate(files):
-                        local[j] = steps[k]
-                    tail_box["voted"] = "failed"        # (until the vote has gone through)
-                    total = np.asarray(owner.global_steps(local), dtype=np.int64)
-                    tail_box["voted"] = "ok"
-                    step0 = np.concatenate([[0], np.cumsum(total)])
-                    if step0[-1] >= (1 << 31) - 1:
-                        raise DkError("owner mode: more than 2^31 commit-tail batches")
-                    base = (C.c_int32 * max(1, len(files)))(*[int(step0[j]) for j in files])
-                    check(lib().dk_json_tail_rebase_steps(tail._h, base))
-                    row0 = (C.c_int64 * (len(files) + 1))()
-                    check(lib().dk_json_tail_file_row0(tail._h, row0))
-                    self.tail_file_rows = [(files[k], int(row0[k]), int(row0[k + 1])) for k in range(len(files))]
-                tail_box["ms"] = (time.perf_counter() - t) * 1e3
-                t = time.perf_counter()
-                rh = C.c_void_p()
-                check(lib().dk_replay_create(engine._h, tail._h, None, C.byref(rh)))
-                tail_box["rh"] = rh
-                tail_box["create_ms"] = (time.perf_counter() - t) * 1e3
-            except BaseException as e:          # re-raised on the calling thread
-                tail_box["error"] = e
-
-        def owner_failed():
-            """This rank is about to raise from prepare: make sure its peers raise too instead of
-            waiting for it in a collective (global_steps, or the exchange's first vote)."""
-            if owner is None or tail_box.get("voted") == "failed":
-                return                      # (a failed vote: every rank raised at global_steps)
-            if not tail_box.get("voted"):
-                owner.global_steps(np.zeros(n_files_all, np.int64), failed=True)
-            else:
-                owner.abort()               # global_steps went through: the exchange's first vote
-
-        tail_thread = threading.Thread(target=parse_tail, daemon=True)
-        started = []
-
-        def start_tail():
-            if not started:
-                started.append(1)
-                tail_thread.start()
+        # the commit tail is parsed (host threads, GIL released in the library) while the checkpoint
+        # files are opened below
+        tp = _TailParse(self, engine, commits, parts, n_files_all)
         try:
-            self._prepare_checkpoint(engine, t0, start_tail)
-            start_tail()
+            self._prepare_checkpoint(engine, t0, tp.start)
+            tp.start()                      # at the latest here (a scan without a checkpoint open to wait for)
         except BaseException as e:
-            if started:                             # the tail's errors come first in replay order
-                tail_thread.join()
-                self.tail = tail_box.get("tail")    # freed by close()
-                self._rh = tail_box.get("rh")
+            if tp.started:
+                tp.join()
+                self.tail, self._rh = tp.tail, tp.rh    # what exists is stored even now: close() frees it
             try:
-                owner_failed()
+                tp.fail_peers()
             finally:
-                if "error" in tail_box:
-                    raise tail_box["error"]
-                raise e
-        tail_thread.join()
-        if "tail" in tail_box:
-            self.tail = tail_box["tail"]
-        if "rh" in tail_box:
-            self._rh = tail_box["rh"]
-        if "error" in tail_box:
-            owner_failed()
-            raise tail_box["error"]
-        self.prepare_ms["commit_tail"] = tail_box["ms"]
-        self.prepare_ms["replay_create_tail"] = tail_box["create_ms"]
+                # both failed: the tail's error is raised (it comes first in the reference's replay order)
+                raise e if tp.error is None else tp.error
+        tp.join()
+        self.tail, self._rh = tp.tail, tp.rh            # stored before a tail error is raised: close() frees them
+        if tp.error is not None:
+            tp.fail_peers()
+            raise tp.error
+        self.prepare_ms["commit_tail"] = tp.ms
+        self.prepare_ms["replay_create_tail"] = tp.create_ms
         try:
             t3 = time.perf_counter()
             if self.ckpt is not None:
                 check(lib().dk_replay_attach_checkpoint(self._rh, self.ckpt._h))
             self.prepare_ms["replay_attach"] = (time.perf_counter() - t3) * 1e3
-            if getattr(self, "exchange", None) is not None and self.shard and self.shard[0] > 1:
-                check(lib().dk_replay_set_exchange(self._rh, self.shard[0], self.shard[1]))
-            if getattr(self, "owner", None) is not None:
+            if self.owner is not None:
                 check(lib().dk_replay_set_owner(self._rh, self.shard[0], self.shard[1]))
+            elif self.exchanging:
+                check(lib().dk_replay_set_exchange(self._rh, self.shard[0], self.shard[1]))
             if self.partition is not None:
                 check(lib().dk_replay_set_partition_filter(self._rh, self.partition.handle))
             if self.skipping is not None:
                 check(lib().dk_replay_set_skipping(self._rh, self.skipping[1].handle))
         except BaseException:
-            owner_failed()
+            tp.fail_peers()                 # (the vote has passed by now: owner.abort)
             raise
         return self
 
@@ -1798,7 +1694,7 @@ class GpuScan:
         # checkpoint batch (ActiveAddFilesIterator.java:158-183, `if (!isFromCheckpoint)`) and only its
         # add rows reach the scan files, so the fused engine pushes that into the projection (the
         # commit tail's removes are parsed by the JSON tail parser)
-        leaves = ADD_LEAVES + ([STATS_LEAF] if self.read_stats else [])
+        leaves = scan_leaves(self.read_stats)
         if self.skipping is not None:
             # the typed add.stats_parsed leaves of the program's stats paths: the engine evaluates
             # skipping over them where a checkpoint file carries them with a type that holds the stat
@@ -1814,8 +1710,10 @@ class GpuScan:
         # tail's exchange overlaps the open, and the row exchanges wait for the decode (dk_replay_run)
         filtered = self.skipping is not None or self.partition is not None or self.predicate is not None
         plain = (not filtered or os.environ.get("DK_ASYNC_FILTERED", "1") != "0") and \
-            (scan_groups(len(self.ckpt_files or [])) or self.shard) and os.environ.get("DK_ASYNC_OPEN", "1") != "0"
+            (scan_groups(len(self.ckpt_files)) or self.shard) and os.environ.get("DK_ASYNC_OPEN", "1") != "0"
         late = bool(plain) and bool(self.ckpt_files) and os.environ.get("DK_TAIL_AFTER_OPEN", "1") != "0"
+        # the tail's parse starts before a synchronous open (and before any open with
+        # DK_TAIL_AFTER_OPEN=0), after an asynchronous one has returned
         if not late:
             start_tail()
         self.ckpt = ParquetSet(engine, self.ckpt_files, leaves, groups=sel, async_open=bool(plain)) \
@@ -1846,7 +1744,6 @@ class GpuScan:
         each row there, and only the surviving rows (compact=True) cross to the host. A generator of
         DataBatch in scan-file order. leaves: physical Parquet leaf paths to emit; filter: "remaining"
         (getRemainingFilter()), a Predicate over the table's logical columns, or None."""
-        from urllib.parse import unquote
         from . import programs, schema
         state = self.getScanState(engine)
         pred = self.getRemainingFilter() if isinstance(filter, str) and filter == "remaining" else filter
@@ -1858,17 +1755,12 @@ class GpuScan:
                 pred = _physical_predicate(pred, schema.parse(state["logicalSchemaString"]), physical)
             prog = programs.compile_data_filter(pred, state["physicalDataReadSchemaString"])
         root = self.table_root()
-        files = []
-        for b in self.getScanFiles(engine):
-            for r in b.selected_rows():
-                r = int(r)
-                files.append((b.data["add.path"].string(r).decode(), _dv_of(b.data, r), _partition_values_of(b.data, r)))
+        files = selected_scan_files(self, engine)
         with_dv = [dv for _, dv, _ in files if dv is not None]
         dvs = DeletionVectors(engine, root, with_dv) if with_dv else None
         dv_index, local, k = [], [], 0
         for path, dv, _ in files:
-            full = path if re.match(r"^[A-Za-z][A-Za-z0-9+.-]*:", path) else root.rstrip("/") + "/" + unquote(path)
-            local.append(full[5:] if full.startswith("file:") else full)
+            local.append(data_file_path(root, path))
             dv_index.append(-1 if dv is None else k)
             k += dv is not None
         ids = {leaf: _leaf_field_ids(physical, leaf) for leaf in leaves} if mapped else None
@@ -1886,7 +1778,7 @@ class GpuScan:
                 prog.close()
 
     def _close_scan_readers(self):
-        for rd in list(getattr(self, "_scan_readers", ())):
+        for rd in list(self._scan_readers):
             rd.close()
         self._scan_readers = weakref.WeakSet()
 
@@ -1894,13 +1786,13 @@ class GpuScan:
         """The device step: commit-tail keys + table, checkpoint decode, probe, selection (with an
         exchange: decode + routing, the exchange, then the probe of the rows the owners flagged)."""
         self._synced = False
-        if getattr(self, "owner", None) is not None:
+        if self.owner is not None:
             # the commit-tail exchange, dk_replay_run and the row exchanges, all in the library
             # (dk_replay_owner_run over the owner's dk_comm)
             self.owner.run_scan(self)
             return
         check(lib().dk_replay_run(self._rh))
-        if getattr(self, "exchange", None) is not None and self.shard and self.shard[0] > 1:
+        if self.exchanging:
             from .shard import ExchangeSide
             self.exchange(ExchangeSide(self))
 
@@ -1953,7 +1845,7 @@ class GpuScan:
             self.prepare(engine)
             self.replay = True
             self._synced = False
-        if not getattr(self, "_synced", False):
+        if not self._synced:
             self._detach_batches()
             self._close_scan_readers()
             self.run()
@@ -1978,9 +1870,8 @@ class GpuScan:
             self._detach_batches()          # the rerun reuses the pinned blocks earlier batches view
             self._close_scan_readers()
         t0 = time.perf_counter()
-        groups = scan_groups(len(self.ckpt_files or []))
-        owner = getattr(self, "owner", None)
-        exchanging = owner is not None or (getattr(self, "exchange", None) is not None and self.shard and self.shard[0] > 1)
+        groups = scan_groups(len(self.ckpt_files))
+        owner = self.owner
         if owner is not None and self.ckpt is not None:
             # owner mode: add.size goes to host memory right after the decode, beside the exchanges.
             # A failure here must still reach the peers (they are about to vote in the owner run):
@@ -1994,7 +1885,7 @@ class GpuScan:
             except BaseException:
                 owner.abort()
                 raise
-        if groups and not exchanging:
+        if groups and not self.exchanging:
             # grouped: batches go out as their group of files is decoded and probed; the counters are
             # final once the iterator is exhausted (ScanImpl's metrics are read after it, too)
             # add.size (split planning reads it from every scan file) goes to host memory as each
@@ -2011,48 +1902,38 @@ class GpuScan:
         self.prepare_ms["device_run"] = (time.perf_counter() - t0) * 1e3
         return self._batches()
 
+    def _tail_batches(self, root, leaves):
+        """The commit tail's batches: the commit files' rows as "json-tail", then a V2 JSON manifest's
+        rows as the first checkpoint batch (ActionsIterator reads the manifest before its sidecars).
+        Owner mode: one batch per file this rank parsed (the manifest on rank 0), tagged with its
+        replay-order index (commit_index) so that the ranks' batches merge in the reference's order."""
+        tail = self.tail
+        if not tail.rows:
+            return
+        sel = np.zeros(tail.rows, dtype=np.uint8)
+        check(lib().dk_replay_json_selection(self._rh, sel.ctypes.data, tail.rows))
+        if self.owner is not None:
+            n_commits = len(self.snapshot.log_segment.deltas)
+            pieces = [(a, b, j >= n_commits, j) for j, a, b in self.tail_file_rows]
+        else:
+            r0 = int(tail.ckpt_row0)
+            pieces = [(0, r0, False, -1), (r0, tail.rows, True, -1)]
+        for a, b, manifest, j in pieces:
+            if b > a:
+                cols = LazyColumns(leaves, lambda leaf, a=a, b=b: tail.column(leaf).slice_rows(a, b))
+                source = self.snapshot._json_checkpoint_parts()[0] if manifest else "json-tail"
+                yield FilteredColumnarBatch(cols, root, b - a, sel[a:b].view(bool), source, commit_index=j)
+
     def _batches(self, grouped=False):
         root = self.table_root()
-        leaves = ADD_LEAVES + ([STATS_LEAF] if self.read_stats else [])
-        if self.tail.rows and getattr(self, "owner", None) is not None:
-            # owner mode: this rank's commit files, one batch each, tagged with their replay-order
-            # index (commit_index) so that the ranks' batches merge in the reference's order
-            sel = np.zeros(self.tail.rows, dtype=np.uint8)
-            check(lib().dk_replay_json_selection(self._rh, sel.ctypes.data, self.tail.rows))
-            n_commits = len(self.snapshot.log_segment.deltas)
-            for j, a, b in self.tail_file_rows:
-                if b <= a:
-                    continue
-                cols = LazyColumns(leaves, lambda leaf, a=a, b=b: self.tail.column(leaf).slice_rows(a, b))
-                if j < n_commits:
-                    fb = FilteredColumnarBatch(cols, root, b - a, sel[a:b].view(bool), "json-tail")
-                else:                       # the V2 JSON manifest's rows (rank 0): first checkpoint batch
-                    fb = FilteredColumnarBatch(cols, root, b - a, sel[a:b].view(bool),
-                                               self.snapshot._json_checkpoint_parts()[0], -1, 0)
-                fb.commit_index = j
-                self._handed[id(fb)] = fb
-                yield fb
-        elif self.tail.rows:
-            sel = np.zeros(self.tail.rows, dtype=np.uint8)
-            check(lib().dk_replay_json_selection(self._rh, sel.ctypes.data, self.tail.rows))
-            r0 = int(self.tail.ckpt_row0)
-            if r0 > 0:
-                cols = LazyColumns(leaves, self.tail.column)
-                fb = FilteredColumnarBatch(cols, root, r0, sel[:r0].view(bool), "json-tail")
-                self._handed[id(fb)] = fb
-                yield fb
-            if r0 < self.tail.rows:
-                # a V2 JSON manifest's rows: the first checkpoint batch (ActionsIterator reads the
-                # manifest before its sidecars)
-                cols = LazyColumns(leaves, lambda leaf: self.tail.column(leaf).slice_rows(r0, self.tail.rows))
-                fb = FilteredColumnarBatch(cols, root, int(self.tail.rows - r0), sel[r0:].view(bool),
-                                           self.snapshot._json_checkpoint_parts()[0], -1, 0)
-                self._handed[id(fb)] = fb
-                yield fb
+        leaves = scan_leaves(self.read_stats)
+        for fb in self._tail_batches(root, leaves):
+            self._handed[id(fb)] = fb
+            yield fb
         # checkpoint batches: zero-copy views of the library's pinned selection bytes and column
         # mirrors (every file's selection comes to the host in one round of copies; a leaf's first
         # access queues its copy for every later file), valid until the scan is closed
-        for fi, path in enumerate(self.ckpt_files or []):
+        for fi, path in enumerate(self.ckpt_files):
             if grouped:
                 check(lib().dk_replay_wait_file(self._rh, fi))
             n = self.ckpt.num_rows(fi)
@@ -2074,7 +1955,7 @@ class GpuScan:
         column mirrors (zero-copy). Before a rerun or close recycles those blocks, every batch still
         referenced gets its own copies of its selection and of every leaf, so that it stays valid
         after the iterator and the scan are closed, as the reference's batches do."""
-        live = list(getattr(self, "_handed", {}).values())
+        live = list(self._handed.values())
         self._handed = weakref.WeakValueDictionary()
         for b in live:
             if b.selection is not None:
@@ -2092,15 +1973,14 @@ class GpuScan:
     def close(self):
         t0 = time.perf_counter()
         self._close_scan_readers()
-        if getattr(self, "_handed", None):
+        if self._handed:
             self._detach_batches()
         t1 = time.perf_counter()
-        if getattr(self, "_rh", None):
+        if self._rh:
             lib().dk_replay_free(self._rh)
             self._rh = None
         t2 = time.perf_counter()
-        for o in ("ckpt", "tail"):
-            x = getattr(self, o, None)
+        for x in (self.ckpt, self.tail):
             if x is not None:
                 x.close()
         t3 = time.perf_counter()

@@ -17,14 +17,15 @@ import json
 import struct
 from decimal import Decimal
 
-from ._lib import DkError, lib
+from ._lib import DkError, Handle, lib
 from .expressions import Column, Literal, Predicate
 
 STATUS_UNSUPPORTED_EXPRESSION = 3        # the reference's evaluator throws for this predicate
 
 
-class Program:
+class Program(Handle):
     """A compiled dk_program (owned; freed on close / garbage collection)."""
+    _free_fn = "dk_program_free"
 
     def __init__(self, handle):
         self._h = handle
@@ -47,17 +48,6 @@ class Program:
     def paths(self):
         """Skipping: the stats paths the program reads (tuples of names), in program order."""
         return [tuple(p["path"]) for p in self.describe().get("paths", [])]
-
-    def close(self):
-        if self._h:
-            lib().dk_program_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _raise(rc, unsupported_cls):

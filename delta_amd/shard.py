@@ -26,6 +26,8 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 
+from ._lib import BatchReader, Handle
+
 
 def owned_files(n_files: int, world: int, rank: int) -> list:
     """Replay-order indices of the checkpoint files rank `rank` reconciles."""
@@ -380,12 +382,13 @@ def _ptr_array(ptr, n, dtype):
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=(n,))
 
 
-class OwnerComm:
+class OwnerComm(Handle):
     """One rank's dk_comm: ScanBuilder.withShard(world, rank, owner=OwnerComm...). The scan's
     prepare() all-reduces the commit files' batch counts through it (global_steps), run() hands the
     replay to dk_replay_owner_run, which runs the three exchanges and their votes in the library.
     Build with OwnerComm.rccl (RCCL over xGMI, the product), OwnerComm.over_torch (callbacks over a
     torch.distributed group: gloo on the CPU) or OwnerComm.local (every rank in this process)."""
+    _free_fn = "dk_comm_destroy"
 
     def __init__(self, handle, world, rank, keep=(), steps=None):
         self._h = handle
@@ -547,18 +550,6 @@ class OwnerComm:
         self._last_run()
         self._status(rc, ad.error)
 
-    def close(self):
-        from ._lib import lib
-        if self._h:
-            lib().dk_comm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:                    # noqa: BLE001 -- interpreter shutdown
-            pass
-
 
 class _SideAdapter:
     """dk_owner_side over a Python object whose calls take and return CPU torch tensors (the layout
@@ -670,20 +661,20 @@ def run_local(scans):
 # streams in the library (ScanFileMerge). A multi-process world needs no collective for this: each
 # process hands its batches to the consumer, which orders them by `order`.
 # ------------------------------------------------------------------------------------------------
-class ScanFileMerge:
+class ScanFileMerge(BatchReader):
     """dk_scan_merge over the rank readers (kernel.ScanFileReader) of one scan, reader i being
     rank i's: next_raw() -> (dk_batch pointer, selection address or None, rank) in getScanFiles'
     order, None at the end; iterating yields ScanFileBatch copies with `order` and `rank` set.
     The merge looks at most one batch ahead per reader. close() leaves the readers open (their
     owner closes them, before or after); batches stay valid after both."""
+    _free_fn = "dk_scan_merge_close"
 
     def __init__(self, readers):
         import ctypes as C
-        from ._lib import check, lib
+        from ._lib import lib
         self.readers = list(readers)
         hs = (C.c_void_p * max(1, len(self.readers)))(*[rd._h for rd in self.readers])
-        self._h = C.c_void_p()
-        check(lib().dk_scan_merge_open(hs, len(self.readers), C.byref(self._h)))
+        self._open(lib().dk_scan_merge_open, hs, len(self.readers))
 
     def next_raw(self):
         import ctypes as C
@@ -695,37 +686,10 @@ class ScanFileMerge:
         check(lib().dk_scan_batch_selection(out, C.byref(sel)))
         return out, sel.value, int(rank.value)
 
-    @staticmethod
-    def release(raw):
-        from ._lib import lib
-        lib().dk_batch_release(raw)
-
-    def __iter__(self):
-        return self
-
-    def __next__(self):
-        got = self.next_raw()
-        if got is None:
-            raise StopIteration
-        raw, sel, rank = got
-        try:
-            b = self.readers[rank].batch(raw, sel)
-            b.rank = rank
-            return b
-        finally:
-            self.release(raw)
-
-    def close(self):
-        from ._lib import lib
-        if self._h:
-            lib().dk_scan_merge_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:                    # noqa: BLE001 -- interpreter shutdown
-            pass
+    def batch(self, raw, sel, rank):
+        b = self.readers[rank].batch(raw, sel)
+        b.rank = rank
+        return b
 
 
 def merged_scan_file_batches(scans, compact=True, batch_rows=None, window_rows=0, leaves=None, emit_tail_rank=0):
