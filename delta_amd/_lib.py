@@ -45,6 +45,16 @@ class dk_column(C.Structure):
                 ("fixed", C.c_void_p), ("offs", C.c_void_p), ("chars", C.c_void_p)]
 
 
+class dk_nest_level(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("list_def", C.c_int32), ("n_parent", C.c_int64), ("n_elem", C.c_int64),
+                ("parent_def", C.c_void_p), ("offs", C.c_void_p)]
+
+
+class dk_batch_nest_level(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("list_def", C.c_int32), ("n_parent", C.c_int64), ("n_elem", C.c_int64),
+                ("first", C.c_int64), ("parent_def", C.c_void_p), ("offs", C.c_void_p)]
+
+
 class dk_parsed_column(C.Structure):
     _fields_ = [("type", C.c_int32), ("n", C.c_int64), ("validity", C.c_void_p), ("values", C.c_void_p),
                 ("values_hi", C.c_void_p), ("scale", C.c_void_p), ("wide", C.c_void_p), ("offs", C.c_void_p),
@@ -157,7 +167,8 @@ EXPORTS = ["dk_last_error", "dk_version", "dk_engine_create", "dk_engine_destroy
            "dk_replay_scan_open", "dk_scan_next", "dk_scan_stats", "dk_scan_close",
            "dk_data_compile", "dk_data_scan_open", "dk_parquet_snappy_serial",
            "dk_replay_scan_open_rank", "dk_scan_batch_order", "dk_scan_batch_selection", "dk_scan_merge_open",
-           "dk_scan_merge_next", "dk_scan_merge_close", "dk_replay_counters_sum"]
+           "dk_scan_merge_next", "dk_scan_merge_close", "dk_replay_counters_sum",
+           "dk_parquet_column_nest", "dk_batch_nest", "dk_parquet_kernel_stats"]
 
 
 def lib(build_if_missing=True):
@@ -192,6 +203,9 @@ def lib(build_if_missing=True):
         "dk_parquet_decode": (C.c_int, [P]), "dk_parquet_sync": (C.c_int, [P]),
         "dk_parquet_num_rows": (I64, [P, I32]),
         "dk_parquet_column": (C.c_int, [P, I32, I32, C.POINTER(dk_column)]),
+        "dk_parquet_column_nest": (C.c_int, [P, I32, I32, I32, C.POINTER(dk_nest_level)]),
+        "dk_batch_nest": (C.c_int, [C.POINTER(dk_batch), I32, I32, C.POINTER(dk_batch_nest_level)]),
+        "dk_parquet_kernel_stats": (C.c_int, [P, I32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(I64)]),
         "dk_parquet_first_row": (C.c_int, [P, I32, I32, I32, C.POINTER(I64)]),
         "dk_parquet_column_rows": (C.c_int, [P, I32, I32, I64, I64, C.POINTER(dk_column)]),
         "dk_parquet_find_bytes": (C.c_int, [P, I32, I32, C.c_char_p, I32, I64, C.POINTER(I64)]),
@@ -392,6 +406,9 @@ class Column:
         self.present = bool(c.present)
         self.n_rows = c.n_rows
         self.phys, self.width, self.max_def, self.max_rep, self.rep_def = c.phys, c.width, c.max_def, c.max_rep, c.rep_def
+        # nested leaf (max_rep >= 2): (list_def, parent_def, offs) per depth 1..max_rep (dk_nest_level);
+        # filled by the reader that knows the handle (ParquetSet.column)
+        self.nest = []
         n_val = c.n_entries if c.max_rep > 0 else c.n_rows
         self.row_def = _arr(c.row_def, c.n_rows, np.uint8) if c.present else np.zeros(c.n_rows, np.uint8)
         self.row_offs = _arr(c.row_offs, c.n_rows + 1, np.int64) if c.max_rep > 0 else None

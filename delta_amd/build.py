@@ -9,7 +9,7 @@ OUT = os.path.join(HERE, "libdkgpu.so")
 OBJ = os.path.join(HERE, "..", "build", "obj")   # kept between builds: only stale objects recompile
 SOURCES = ["dk_host.cpp", "dk_expr.cpp", "dk_comm.cpp", "dk_kernels.hip", "dk_arrow.hip", "dk_dv.hip", "dk_encode.hip",
            "dk_export.hip", "dk_lookup.hip", "dk_zstd.hip"]
-HEADERS = ["dk_device.h", "dk_thrift.h", "dk_uri.h", "dk_expr.h", "dk_zstd.h"]
+HEADERS = ["dk_device.h", "dk_thrift.h", "dk_uri.h", "dk_expr.h", "dk_zstd.h", "dk_nest.h"]
 
 
 def _stale():

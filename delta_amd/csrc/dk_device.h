@@ -13,6 +13,7 @@ struct DChunk {
   int32_t dict_page;     // page index of the dictionary page, -1 if none
   int64_t dict_pos;      // string dictionaries: scratch offset (int32 per entry + 1)
   int64_t dict_hash_off; // key columns: offset of this chunk's dictionary entries in DColumn.dhash
+  int32_t list_def[4];   // definition level of the k-th repeated node of the leaf's path at [k - 1] (dk_nest.h)
 };
 
 // PF_POS: a BYTE_ARRAY data page whose chars are placed through its position slots (PLAIN: k_pos_*, the
@@ -153,6 +154,26 @@ struct DColumn {
   uint64_t* vhash;
   uint64_t* hash;
   uint64_t* dhash;       // key columns: path hash of every dictionary entry (k_string_copy)
+  int32_t list_def[4];   // definition level of the k-th repeated node of the leaf's path at [k - 1] (dk_nest.h)
+  int32_t nest;          // max_rep >= 2: 1 + the column's index in the nest table (DNest); else 0
+  int32_t pad_nest;
+};
+
+// Nested leaves (max_rep = R >= 2, dk_nest.h): the depth-k elements, k = 1..R-1, of one level tile
+// (k_nest_count; bases within the column from k_nest_scan) -- depth 0 (rows) and depth R (entries)
+// are DTile's. One DNestTile per level tile of a nested column, in tile order.
+struct DNestTile {
+  int32_t n[3], pad;
+  int64_t base[3];
+};
+// One nested column's structure: per depth k = 1..R the offsets of the depth-k elements within the
+// depth-(k-1) elements, and for k < R the definition level at each depth-k element's first level.
+struct DNest {
+  int32_t col;           // DColumn index
+  int32_t first_ntile;   // DNestTile of the column's first level tile
+  int64_t n[5];          // n_0..n_R (k_nest_scan: n[0] rows, n[R] entries)
+  int64_t* offs[4];      // offs_k at [k - 1]: n_{k-1} + 1 entries (null while the outputs are being sized)
+  uint8_t* def[3];       // def_k at [k - 1], k = 1..R-1: n_k entries
 };
 
 // streaming reader: one leaf's window of batches -> validity bits + int32 offsets (dk_arrow.hip)

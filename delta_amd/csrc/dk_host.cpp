@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cctype>
 #include <climits>
 #include <cstdio>
@@ -31,6 +32,7 @@
 #include "dk_uri.h"
 #include "dk_expr.h"
 #include "dk_zstd.h"
+#include "dk_nest.h"
 
 namespace dk {
 void launch_page_headers(const DChunk*, DPage*, int, hipStream_t);
@@ -57,6 +59,9 @@ void launch_tile_scan1(DColumn*, int, DPage*, DTile*, DState*, hipStream_t);
 void launch_tile_chars(const DChunk*, DPage*, const uint8_t*, const int32_t*, const Seg*, DTile*, int, int, hipStream_t);
 void launch_tile_scan2(DColumn*, int, DPage*, DTile*, DState*, hipStream_t);
 void launch_tile_decode(const DChunk*, DPage*, const DColumn*, const uint8_t*, const int32_t*, const long long*, const Seg*, const DTile*, int, int, DState*, hipStream_t);
+void launch_nest_count(const DChunk*, const DPage*, const DColumn*, const uint8_t*, const Seg*, const DTile*, DNestTile*, DNest*, int, hipStream_t);
+void launch_nest_scan(const DColumn*, DNestTile*, DNest*, hipStream_t);
+void launch_nest_fill(const DChunk*, const DPage*, const DColumn*, const uint8_t*, const Seg*, const DTile*, const DNestTile*, const DNest*, int, hipStream_t);
 void launch_delta_decode(const DChunk*, DPage*, int, const uint8_t*, long long*, hipStream_t);
 void launch_delta_lengths(const DChunk*, DPage*, int, const uint8_t*, int32_t*, int32_t*, hipStream_t);
 void launch_bss_gather(const DChunk*, DPage*, int, const uint8_t*, long long*, hipStream_t);
@@ -609,6 +614,7 @@ struct LeafM {
   std::string path; int phys, type_length, max_def, max_rep, rep_def;
   int leaf_rep = 0, lt = LT_NONE, int_bits = 0, int_signed = 1;   // own repetition, logical type
   int ts_unit = 0, dec_scale = -1;      // timestamp unit (1 ms, 2 us, 3 ns; INT96 = 4), decimal scale
+  int list_def[DK_NEST_MAX] = {0, 0, 0, 0};   // definition level of the k-th repeated node of the path at [k - 1]
 };
 // A checkpoint file as the decoder sees it: the footer, plus only the byte ranges of the
 // projected column chunks (and their offset indexes), read with pread -- parquet-mr's column
@@ -827,9 +833,9 @@ static int parse_footer(FileM& f) {
   }
   if (t.bad || f.schema.empty()) return fail("Error reading Parquet file: " + f.path + " (corrupt footer)");
   // leaves (DFS over the flattened schema)
-  struct Fr { int remaining, def, rep, rep_def; std::string path; int el; };
+  struct Fr { int remaining, def, rep, rep_def; std::string path; int el; int list_def[DK_NEST_MAX]; };
   std::vector<Fr> st;
-  st.push_back({f.schema[0].num_children, 0, 0, 0, "", 0});
+  st.push_back({f.schema[0].num_children, 0, 0, 0, "", 0, {0, 0, 0, 0}});
   size_t pos = 1;
   while (!st.empty()) {
     if (st.back().remaining == 0) { st.pop_back(); continue; }
@@ -843,9 +849,15 @@ static int parse_footer(FileM& f) {
     int rep = top.rep + (e.repetition == 2 ? 1 : 0);
     int rep_def = e.repetition == 2 ? def : top.rep_def;
     std::string path = top.path.empty() ? e.name : top.path + "." + e.name;
-    if (e.num_children > 0) st.push_back({e.num_children, def, rep, rep_def, path, (int)pos - 1});
-    else {
+    int list_def[DK_NEST_MAX];
+    memcpy(list_def, top.list_def, sizeof list_def);
+    if (e.repetition == 2 && rep <= DK_NEST_MAX) list_def[rep - 1] = def;
+    if (e.num_children > 0) {
+      st.push_back({e.num_children, def, rep, rep_def, path, (int)pos - 1, {0, 0, 0, 0}});
+      memcpy(st.back().list_def, list_def, sizeof list_def);
+    } else {
       LeafM L{path, e.type, e.type_length, def, rep, rep_def};
+      memcpy(L.list_def, list_def, sizeof list_def);
       L.leaf_rep = e.repetition;
       // parquet-mr: the LogicalType when set, else the ConvertedType (UTF8 0, DATE 6, INT_8..INT_64
       // 15..18, UINT_8..UINT_64 11..14)
@@ -1042,13 +1054,14 @@ static int phys_width(int phys, int tl) {
 // kernel timing (HIP events on the engine stream)
 // ------------------------------------------------------------------------------------------------
 struct KTimer {
-  static constexpr int K = 30;
+  static constexpr int K = 32;
   const char* names[K] = {"k_page_headers", "k_delta_lengths", "k_tile_count", "k_tile_scan",
                           "k_string_positions", "k_tile_decode", "k_string_copy", "k_json_canon",
                           "k_table_insert", "k_table_update", "k_json_select", "k_probe", "step_total",
                           "k_snap_walk_link", "k_delta_decode", "k_page_runs", "k_tile_chars", "k_stats_eval", "k_part_eval",
                           "k_snap_fix", "k_snap_frag", "k_snappy_serial", "k_owner_route", "k_owner_resolve",
-                          "k_bss_gather", "k_dlba_copy", "k_dba_tail", "k_dba_link", "k_dba_expand", "k_zstd_page"};
+                          "k_bss_gather", "k_dlba_copy", "k_dba_tail", "k_dba_link", "k_dba_expand", "k_zstd_page",
+                          "k_nest_count", "k_nest_fill"};
   double sum_ms[K] = {0};
   int64_t cnt[K] = {0};
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
@@ -1090,10 +1103,12 @@ struct HostMirror {
   int state = 0;            // 0 empty, 1 copy queued (wait on ev), 2 ready
   hipEvent_t ev = nullptr;
   HBuf row_def, row_offs, entry_def, fixed, offs, chars;
+  std::vector<HBuf> nest;   // nested leaf: offs_1..offs_R, then def_1..def_{R-1} (dk_parquet_column_nest)
   HostMirror() = default;
   HostMirror(const HostMirror&) = delete;
   HostMirror(HostMirror&& o) noexcept : state(o.state), ev(o.ev), row_def(std::move(o.row_def)), row_offs(std::move(o.row_offs)),
-      entry_def(std::move(o.entry_def)), fixed(std::move(o.fixed)), offs(std::move(o.offs)), chars(std::move(o.chars)) { o.ev = nullptr; }
+      entry_def(std::move(o.entry_def)), fixed(std::move(o.fixed)), offs(std::move(o.offs)), chars(std::move(o.chars)),
+      nest(std::move(o.nest)) { o.ev = nullptr; }
   ~HostMirror() { if (ev) hipEventDestroy(ev); }
 };
 
@@ -1143,6 +1158,10 @@ struct dk_parquet {
   int n_cpages = 0, n_frags = 0, n_segs = 0;
   DBuf d_ltiles, d_runs;     // level tiles (DTile) and hybrid-stream run tables (Seg)
   int n_ltiles = 0;
+  // nested leaves (max_rep >= 2, dk_nest.h): one DNest per such column and one DNestTile per level
+  // tile of theirs; empty and unallocated when no nested leaf is projected
+  std::vector<DNest> h_nest;
+  DBuf d_nest, d_ntiles;
   DBuf d_pchunks;            // string-position chunks (DPosChunk)
   DBuf d_pos_scratch;        // k_pos_count's candidates, DK_POS_CAP int16 offsets per chunk
   int n_pchunks = 0;
@@ -1257,6 +1276,31 @@ static PRange file_range(const dk_parquet* p, int f0, int f1) {
   return R;
 }
 
+// Nested leaves among columns [c0, c1) (dk_nest.h; none: nothing is launched). stage 0: element
+// counts per tile and their scan (after k_tile_scan1, which gives the entries); 1: the scan alone
+// (the closing offsets into freshly allocated outputs); 2: the fill, with the value decode
+static void nest_stage(dk_parquet* p, hipStream_t s, int c0, int c1, int stage) {
+  if (p->h_nest.empty()) return;
+  KTimer& T = p->timer;
+  const DChunk* C = p->d_chunks.as<DChunk>();
+  const DPage* P = p->d_pages.as<DPage>();
+  const DColumn* cols = p->d_cols.as<DColumn>();
+  const uint8_t* arena = p->d_arena.as<uint8_t>();
+  const DTile* LT = p->d_ltiles.as<DTile>();
+  const Seg* runs = p->d_runs.as<Seg>();
+  DNestTile* NTl = p->d_ntiles.as<DNestTile>();
+  for (size_t k = 0; k < p->h_nest.size(); k++) {
+    const int ci = p->h_nest[k].col;
+    if (ci < c0 || ci >= c1) continue;
+    DNest* N = p->d_nest.as<DNest>() + k;
+    const int nt = p->h_cols[ci].n_tiles;
+    KTimer::Scope sc(&T, stage == 2 ? 31 : 30, s);
+    if (stage == 0) launch_nest_count(C, P, cols, arena, runs, LT, NTl, N, nt, s);
+    if (stage <= 1) launch_nest_scan(cols, NTl, N, s);
+    if (stage == 2) launch_nest_fill(C, P, cols, arena, runs, LT, NTl, N, nt, s);
+  }
+}
+
 // headers, snappy, runs, counts, positions, chars and the scans over one slice
 static void sizing_stages(dk_parquet* p, hipStream_t s, const PRange& R) {
   KTimer& T = p->timer;
@@ -1303,6 +1347,7 @@ static void sizing_stages(dk_parquet* p, hipStream_t s, const PRange& R) {
   { KTimer::Scope sc(&T, 15, s); launch_page_runs(C, P + R.pa, np, arena, runs, s); }
   { KTimer::Scope sc(&T, 2, s); launch_tile_count(C, P, arena, runs, LT, R.t1 - R.t0, R.t0, s); }
   { KTimer::Scope sc(&T, 3, s); launch_tile_scan1(cols + R.col0, R.col1 - R.col0, P, LT, st, s); }
+  nest_stage(p, s, R.col0, R.col1, 0);
   { KTimer::Scope sc(&T, 4, s); launch_positions(C, P, R.pa, np, arena, pos, p->d_pchunks.as<DPosChunk>(), R.pc0, R.pc1 - R.pc0,
                                                     p->d_pos_scratch.as<int16_t>(), s); }
   if (p->has_dlba || p->has_dba) {
@@ -1352,6 +1397,7 @@ static void decode_cols(dk_parquet* p, hipStream_t s, int c0, int c1) {
     const int b = c1 < p->n_cols ? p->h_cols[c1].first_tile : p->n_ltiles;
     if (b > a) launch_tile_decode(C, P, cols, arena, pos, dbp, runs, LT, b - a, a, st, s);
   }
+  nest_stage(p, s, c0, c1, 2);
 }
 
 // the decode pipeline over every file (mode: -1 = headers only; 0 = through the scans, which size the
@@ -1377,6 +1423,7 @@ static int run_pipeline(dk_parquet* p, int mode, hipStream_t s = nullptr, bool f
   if (reuse) {                         // headers, snappy, runs, counts, positions, chars: done by prepare
     { KTimer::Scope sc(&T, 3, s); launch_tile_scan1(cols, p->n_cols, P, LT, st, s); }
     { KTimer::Scope sc(&T, 3, s); launch_tile_scan2(cols, p->n_cols, P, LT, st, s); }
+    nest_stage(p, s, 0, p->n_cols, 1);
   } else {
     { KTimer::Scope sc(&T, 0, s); launch_page_headers(C, P, p->n_pages, s); }
     if (mode == -1) return 0;
@@ -1529,6 +1576,13 @@ static int alloc_outputs(dk_parquet* p, int c0, int c1, const std::vector<DColum
         c.chars = (uint8_t*)mk(c.n_chars);
       } else {
         c.fixed = (uint8_t*)mk(nv * c.width);
+      }
+    }
+    if (c.nest) {                      // offs_k (n_{k-1} + 1) and def_k (n_k) of every depth (dk_nest.h)
+      DNest& N = p->h_nest[c.nest - 1];
+      for (int k = 1; k <= c.max_rep; k++) {
+        N.offs[k - 1] = (int64_t*)mk((size_t)(N.n[k - 1] + 1) * 8);
+        if (k < c.max_rep) N.def[k - 1] = (uint8_t*)mk((size_t)N.n[k]);
       }
     }
     if (!c.row_def) return 1;
@@ -1767,6 +1821,23 @@ static int prepare(dk_parquet* p) {
       c.n_tiles = (int)tbase.back() - c.first_tile;
     }
     p->n_ltiles = (int)tbase.back();
+    // nested leaves: their DNest records and per-tile element counts (dk_nest.h)
+    p->h_nest.clear();
+    int ntile_n = 0;
+    for (size_t ci = 0; ci < p->h_cols.size(); ci++) {
+      DColumn& c = p->h_cols[ci];
+      c.nest = 0;
+      if (c.max_rep < 2) continue;
+      DNest N{};
+      N.col = (int32_t)ci; N.first_ntile = ntile_n;
+      ntile_n += c.n_tiles;
+      p->h_nest.push_back(N);
+      c.nest = (int32_t)p->h_nest.size();
+    }
+    if (!p->h_nest.empty() &&
+        (p->d_ntiles.alloc((size_t)(ntile_n + 1) * sizeof(DNestTile)) ||
+         upload_zc(p, p->d_nest, p->h_nest.data(), p->h_nest.size() * sizeof(DNest), us)))
+      return 1;
     // string-position chunks of every BYTE_ARRAY PLAIN data page and dictionary page (the region
     // is at most the page body; chunks past the region's end find nothing)
     std::vector<int32_t> ppage;
@@ -2006,6 +2077,8 @@ static int prepare(dk_parquet* p) {
   if (!per_slice) {
     HIPOK(hipMemcpyAsync(got.data(), p->d_cols.p, got.size() * sizeof(DColumn), hipMemcpyDeviceToHost, s));
     HIPOK(hipMemcpyAsync(p->h_pages.data(), p->d_pages.p, p->h_pages.size() * sizeof(DPage), hipMemcpyDeviceToHost, s));
+    if (!p->h_nest.empty())                                       // the nested leaves' element counts
+      HIPOK(hipMemcpyAsync(p->h_nest.data(), p->d_nest.p, p->h_nest.size() * sizeof(DNest), hipMemcpyDeviceToHost, s));
   }
   HIPOK(hipStreamSynchronize(s));
   std::string m = page_status_msg(p, p->h_pages);
@@ -2026,6 +2099,7 @@ static int prepare(dk_parquet* p) {
   if (!per_slice) {
     if (upload(p->d_cols, p->h_cols.data(), p->h_cols.size() * sizeof(DColumn), s)) return 1;
     if (upload(p->d_chunks, p->h_chunks.data(), p->h_chunks.size() * sizeof(DChunk), s)) return 1;   // dict_hash_off
+    if (!p->h_nest.empty() && upload(p->d_nest, p->h_nest.data(), p->h_nest.size() * sizeof(DNest), s)) return 1;
   }
   HIPOK(hipStreamSynchronize(s));
   if (per_slice && check_state(p)) return 1;   // decode errors of the per-slice value decode
@@ -2503,10 +2577,11 @@ static int build_file_meta(const dk_parquet* p, int fi, const FileM& f, const st
     const int idx = leafidx[li];
     if (idx < 0) continue;
     const LeafM& L = f.leaves[idx];
-    if (L.max_rep > 1) return fail("Error reading Parquet file: " + f.path + " (nested repetition not supported: " + L.path + ")");
+    if (L.max_rep > DK_NEST_MAX) return fail("Error reading Parquet file: " + f.path + " (nested repetition not supported: " + L.path + ")");
     DColumn c{};
     c.phys = L.phys; c.width = L.phys == PT_BYTE_ARRAY ? 0 : phys_width(L.phys, L.type_length);
     c.max_def = L.max_def; c.max_rep = L.max_rep; c.rep_def = L.rep_def; c.present = 1;
+    memcpy(c.list_def, L.list_def, sizeof c.list_def);
     c.key_hash = p->leaves[li] == "add.path";   // the reconciliation key (ActiveAddFilesIterator)
     c.n_rows = 0;
     c.first_page = (int)M.pages.size();
@@ -2521,6 +2596,7 @@ static int build_file_meta(const dk_parquet* p, int fi, const FileM& f, const st
       ck.file = p->dfile[fi].as<uint8_t>();
       ck.col = colid;
       ck.phys = L.phys; ck.width = c.width; ck.max_def = L.max_def; ck.max_rep = L.max_rep; ck.rep_def = L.rep_def;
+      memcpy(ck.list_def, L.list_def, sizeof ck.list_def);
       ck.codec = m.codec; ck.dict_page = -1; ck.dict_pos = 0;
       const int chunk_id = (int)M.chunks.size();
       std::vector<PageRef> refs;
@@ -2785,7 +2861,11 @@ static int parquet_open(dk_engine* e, const char* const* paths, int32_t n_files,
     p.release();                                  // the caller owns it
     return rc;
   };
-  if (publish) {
+  // a nested leaf (dk_nest.h) takes the synchronous path: its structure is sized and allocated with
+  // the whole set, so the handle is published once the open has finished
+  bool nested = false;
+  for (const DColumn& c : p->h_cols) nested |= c.max_rep > 1;
+  if (publish && !nested) {
     p->async_open = true;
     p->host.resize(p->h_cols.size());            // column mirrors (queued per file as files get ready)
     p->files_ready = 0;
@@ -2864,9 +2944,12 @@ extern "C" int dk_parquet_open_async(dk_engine* e, const char* const* paths, int
     dk_parquet* q = nullptr;
     bool pub = false;
     std::function<void(dk_parquet*)> pub_fn = [&](dk_parquet* x) { pub = true; publish(x); };
-    if (parquet_open(e, paths, n_files, leaves, n_leaves, gp, &q, nullptr, &pub_fn) && !pub) {
+    const int rc = parquet_open(e, paths, n_files, leaves, n_leaves, gp, &q, nullptr, &pub_fn);
+    if (rc && !pub) {
       early_err = g_err;
       handed.set_value(nullptr);
+    } else if (!pub) {
+      handed.set_value(q);                         // opened synchronously (a nested leaf is projected)
     }
   });
   dk_parquet* p = got.get();
@@ -3124,6 +3207,16 @@ static int queue_mirror(dk_parquet* p, int ci) {
     if (c.null_only) memset(h.fixed.data(), 0, nv * c.width + 1);
     else if (nv && d2h(h.fixed.data(), c.fixed, nv * c.width)) return 1;
   }
+  if (c.nest) {                        // offs_1..offs_R, then def_1..def_{R-1}
+    const DNest& N = p->h_nest[c.nest - 1];
+    const int R = c.max_rep;
+    h.nest.clear();
+    h.nest.resize(2 * R - 1);
+    for (int k = 1; k <= R; k++) {
+      if (h.nest[k - 1].alloc((size_t)(N.n[k - 1] + 1) * 8) || d2h(h.nest[k - 1].data(), N.offs[k - 1], (size_t)(N.n[k - 1] + 1) * 8)) return 1;
+      if (k < R && (h.nest[R + k - 1].alloc((size_t)N.n[k] + 1) || d2h(h.nest[R + k - 1].data(), N.def[k - 1], (size_t)N.n[k]))) return 1;
+    }
+  }
   if (!h.ev) HIPOK(hipEventCreateWithFlags(&h.ev, hipEventDisableTiming));
   HIPOK(hipEventRecord(h.ev, s));
   h.state = 1;
@@ -3168,6 +3261,27 @@ extern "C" int dk_parquet_column(dk_parquet* p, int32_t file, int32_t leaf, dk_c
   out->fixed = c.phys == PT_BYTE_ARRAY ? nullptr : h.fixed.data();
   out->offs = c.phys == PT_BYTE_ARRAY ? (const int64_t*)h.offs.data() : nullptr;
   out->chars = c.phys == PT_BYTE_ARRAY ? h.chars.data() : nullptr;
+  return 0;
+}
+
+// One nest level of a nested leaf (max_rep >= 2), from the mirror dk_parquet_column queued
+extern "C" int dk_parquet_column_nest(dk_parquet* p, int32_t file, int32_t leaf, int32_t depth, dk_nest_level* out) {
+  if (!p || !out) return fail("dk_parquet_column_nest: null argument");
+  memset(out, 0, sizeof *out);
+  dk_column col;
+  if (dk_parquet_column(p, file, leaf, &col)) return 1;
+  const int ci = p->colmap[file][leaf];
+  if (ci < 0 || p->h_cols[ci].max_rep <= 1)
+    return fail("dk_parquet_column_nest: " + p->leaves[leaf] + " is not a nested leaf (max_rep <= 1)");
+  const DColumn& c = p->h_cols[ci];
+  if (depth < 1 || depth > c.max_rep)
+    return fail("dk_parquet_column_nest: depth " + std::to_string(depth) + " outside 1.." + std::to_string(c.max_rep) + " (" + p->leaves[leaf] + ")");
+  const DNest& N = p->h_nest[c.nest - 1];
+  HostMirror& h = p->host[ci];
+  out->depth = depth; out->list_def = c.list_def[depth - 1];
+  out->n_parent = N.n[depth - 1]; out->n_elem = N.n[depth];
+  out->parent_def = depth == 1 ? h.row_def.data() : h.nest[c.max_rep + depth - 2].data();
+  out->offs = (const int64_t*)h.nest[depth - 1].data();
   return 0;
 }
 
@@ -3275,6 +3389,9 @@ extern "C" int dk_parquet_column_rows(dk_parquet* p, int32_t file, int32_t leaf,
   out->n_rows = n;
   if (ci < 0) { out->present = 0; return 0; }
   const DColumn& c = p->h_cols[ci];
+  if (c.max_rep > 1)
+    return fail("dk_parquet_column_rows: nested leaf " + p->leaves[leaf] + " (max_rep " + std::to_string(c.max_rep) +
+                "): a row slice cannot carry its structure (dk_parquet_column + dk_parquet_column_nest, or dk_reader_*)");
   HostCol& h = p->slice[ci];
   h = HostCol();
   h.row_def.resize(n);
@@ -5959,6 +6076,18 @@ extern "C" int dk_replay_kernel_stats(dk_replay* r, int32_t i, const char** name
   return 0;
 }
 
+// the decode kernels' timer slots of one set (DK_FLAG_TIMING; the slots dk_replay_kernel_stats reads
+// for an attached checkpoint), after dk_parquet_sync
+extern "C" int dk_parquet_kernel_stats(dk_parquet* p, int32_t i, const char** name, double* avg_us, int64_t* count) {
+  if (!p || i < 0 || i >= KTimer::K) return 1;
+  const KTimer& t = p->timer;
+  *name = t.names[i];
+  if (!*name) return 1;
+  *count = t.cnt[i];
+  *avg_us = t.cnt[i] ? 1000.0 * t.sum_ms[i] / (double)t.cnt[i] : 0.0;
+  return 0;
+}
+
 extern "C" void dk_replay_free(dk_replay* r) {
   if (!r) return;
   hipSetDevice(r->eng->cfg.device);
@@ -6011,6 +6140,12 @@ struct WinLeaf {                 // one leaf's buffers inside a window (offsets 
   int phys = 0, width = 0, max_def = 0, max_rep = 0, rep_def = 0;
   int64_t nv = 0, nchars = 0;
   size_t o_rowdef = 0, o_entdef = 0, o_fixed = 0, o_chars = 0, o_bits = 0, o_offs = 0, o_rowoffs = 0;
+  // nested leaf (max_rep >= 2, dk_nest.h): the window's depth-k elements (ncnt[k], k = 0..R), its
+  // int32 offsets of depth k rebased to the window (o_noffs[k - 1], ncnt[k - 1] + 1 entries) and the
+  // definition levels of its depth-k elements (o_ndef[k - 1], k = 1..R-1)
+  int list_def[DK_NEST_MAX] = {0, 0, 0, 0};
+  int64_t ncnt[DK_NEST_MAX + 1] = {0, 0, 0, 0, 0};
+  size_t o_noffs[DK_NEST_MAX] = {0, 0, 0, 0}, o_ndef[DK_NEST_MAX] = {0, 0, 0, 0};
 };
 
 struct RWin {                    // rows [r0, r0 + nr) of one file in pinned host memory
@@ -6063,6 +6198,7 @@ struct dk_reader : BatchOwner {
 struct dk_batch_impl {
   dk_batch pub;
   std::vector<dk_batch_column> cols;
+  std::vector<dk_batch_nest_level> nest;   // DK_NEST_MAX per column when a nested leaf is projected (dk_batch_nest)
   BatchOwner* rd;
   RWin* win;
   const uint8_t* sel = nullptr;  // scan readers, compact = 0: the batch's selection bytes (in its window)
@@ -6146,7 +6282,7 @@ static int load_window(const WinCtx& X, RWin* w, int64_t r0, int64_t nr) {
   // into pinned memory: one round for the entry ranges, one for the char ranges)
   struct Rng { int64_t v0 = 0, v1 = 0, c0 = 0, c1 = 0; };
   std::vector<Rng> rg(nl);
-  if (X.h_rng->size() < nl * 32 + 64 && X.h_rng->alloc(nl * 32 + 64)) return 1;
+  if (X.h_rng->size() < nl * 48 + 64 && X.h_rng->alloc(nl * 48 + 64)) return 1;
   int64_t* hr = (int64_t*)X.h_rng->data();
   for (;;) {
     bool fits = true;
@@ -6187,10 +6323,37 @@ static int load_window(const WinCtx& X, RWin* w, int64_t r0, int64_t nr) {
     nr = std::max<int64_t>(X.B, nr / 2 / X.B * X.B);           // int32 offsets: a smaller window
   }
   w->nr = nr;
+  // nested leaves: the window's first element of every depth, down the offset chain rows -> depth 1
+  // -> ... -> values (one stream-ordered round per depth)
+  struct NRng { int64_t a[DK_NEST_MAX + 1], b[DK_NEST_MAX + 1]; };
+  std::vector<NRng> nrg(nl);
+  for (size_t li = 0; li < nl; li++) { nrg[li].a[0] = r0; nrg[li].b[0] = r0 + nr; }
+  for (int k = 1; k <= DK_NEST_MAX; k++) {
+    int64_t* hn = hr + 4 * nl + 1;
+    bool any = false;
+    for (size_t li = 0; li < nl; li++) {
+      const int ci = X.col(li);
+      if (ci < 0 || !p->h_cols[ci].nest || k > p->h_cols[ci].max_rep) continue;
+      const DNest& N = p->h_nest[p->h_cols[ci].nest - 1];
+      HIPOK(hipMemcpyAsync(hn + 2 * li, N.offs[k - 1] + nrg[li].a[k - 1], 8, hipMemcpyDeviceToHost, s));
+      HIPOK(hipMemcpyAsync(hn + 2 * li + 1, N.offs[k - 1] + nrg[li].b[k - 1], 8, hipMemcpyDeviceToHost, s));
+      any = true;
+    }
+    if (!any) break;
+    HIPOK(hipStreamSynchronize(s));
+    for (size_t li = 0; li < nl; li++) {
+      const int ci = X.col(li);
+      if (ci < 0 || !p->h_cols[ci].nest || k > p->h_cols[ci].max_rep) continue;
+      nrg[li].a[k] = hn[2 * li]; nrg[li].b[k] = hn[2 * li + 1];
+      if (nrg[li].b[k] - nrg[li].a[k] >= (1ll << 31) - 1)
+        return fail("Error reading Parquet file: " + p->files[fi].path + " (a window's nested elements exceed int32 offsets)");
+    }
+  }
   // host layout, 64-byte aligned pieces; device staging for bits + int32 offsets
   size_t hsz = 0, dsz = 0;
   auto take = [](size_t& at, size_t n) { at = (at + 63) & ~(size_t)63; const size_t o = at; at += n; return o; };
   std::vector<size_t> d_bits(nl), d_offs(nl), d_roffs(nl);
+  std::vector<std::array<size_t, DK_NEST_MAX>> d_noffs(nl);
   for (size_t li = 0; li < nl; li++) {
     const int ci = X.col(li);
     WinLeaf& L = w->leaf[li];
@@ -6202,6 +6365,14 @@ static int load_window(const WinCtx& X, RWin* w, int64_t r0, int64_t nr) {
     L.nv = rg[li].v1 - rg[li].v0;
     L.nchars = rg[li].c1 - rg[li].c0;
     if (c.max_rep > 0) { L.o_entdef = take(hsz, L.nv); L.o_rowoffs = take(hsz, 4 * (nr + 1)); d_roffs[li] = take(dsz, 4 * (nr + 1)); }
+    if (c.nest) {
+      for (int k = 0; k <= c.max_rep; k++) L.ncnt[k] = nrg[li].b[k] - nrg[li].a[k];
+      for (int k = 1; k <= c.max_rep; k++) {
+        L.list_def[k - 1] = c.list_def[k - 1];
+        L.o_noffs[k - 1] = take(hsz, 4 * (L.ncnt[k - 1] + 1)); d_noffs[li][k - 1] = take(dsz, 4 * (L.ncnt[k - 1] + 1));
+        if (k < c.max_rep) L.o_ndef[k - 1] = take(hsz, L.ncnt[k]);
+      }
+    }
     L.o_bits = take(hsz, 8 * ((L.nv + 63) / 64)); d_bits[li] = take(dsz, 8 * ((L.nv + 63) / 64));
     if (c.phys == PT_BYTE_ARRAY) {
       L.o_offs = take(hsz, 4 * (L.nv + 1)); d_offs[li] = take(dsz, 4 * (L.nv + 1));
@@ -6228,6 +6399,20 @@ static int load_window(const WinCtx& X, RWin* w, int64_t r0, int64_t nr) {
     if (ci < 0) { memset(H + L.o_rowdef, 0, nr); continue; }
     const DColumn& c = p->h_cols[ci];
     HIPOK(hipMemcpyAsync(H + L.o_rowdef, c.row_def + r0, nr, hipMemcpyDeviceToHost, s));
+    if (c.nest) {               // the nest levels: offsets rebased to the window on the device, def slices
+      const DNest& N = p->h_nest[c.nest - 1];
+      for (int k = 1; k <= c.max_rep; k++) {
+        ArrowWin A{};
+        A.row_offs = N.offs[k - 1] + nrg[li].a[k - 1];
+        A.nr = L.ncnt[k - 1];
+        A.row_offs32 = (int32_t*)(D + d_noffs[li][k - 1]);
+        A.overflow = X.d_ovf->as<int32_t>();
+        launch_arrow_window(A, s);
+        HIPOK(hipMemcpyAsync(H + L.o_noffs[k - 1], D + d_noffs[li][k - 1], 4 * (L.ncnt[k - 1] + 1), hipMemcpyDeviceToHost, s));
+        if (k < c.max_rep && L.ncnt[k])
+          HIPOK(hipMemcpyAsync(H + L.o_ndef[k - 1], N.def[k - 1] + nrg[li].a[k], L.ncnt[k], hipMemcpyDeviceToHost, s));
+      }
+    }
     if (c.null_only) {          // no value anywhere: all-null values, empty maps
       memset(H + L.o_bits, 0, 8 * ((L.nv + 63) / 64));
       if (c.max_rep > 0) { memset(H + L.o_rowoffs, 0, 4 * (nr + 1)); }
@@ -6280,6 +6465,7 @@ static int load_window(const WinCtx& X, RWin* w, int64_t r0, int64_t nr) {
       if (L.null_only) continue;
       moved += 8 * ((L.nv + 63) / 64);
       if (L.max_rep > 0) moved += 4 * (nr + 1) + L.nv;
+      for (int k = 1; k <= L.max_rep && L.max_rep > 1; k++) moved += 4 * (L.ncnt[k - 1] + 1) + (k < L.max_rep ? L.ncnt[k] : 0);
       moved += L.phys == PT_BYTE_ARRAY ? 4 * (L.nv + 1) + L.nchars : L.nv * L.width;
     }
     *X.d2h += moved;
@@ -6359,6 +6545,20 @@ static dk_batch_impl* make_batch(BatchOwner* o, RWin* w, int64_t rb, int64_t nb)
     }
     if (d.phys == PT_BYTE_ARRAY) { c.offs = (const int32_t*)(H + L.o_offs); c.chars = H + L.o_chars; }
     else c.fixed = H + L.o_fixed;
+    if (d.max_rep > 1) {        // the batch's slice of every nest level, down the offset chain
+      if (b->nest.empty()) b->nest.assign(w->leaf.size() * DK_NEST_MAX, dk_batch_nest_level{});
+      int64_t lo = rb, hi = rb + nb;
+      for (int k = 1; k <= d.max_rep; k++) {
+        dk_batch_nest_level& nl = b->nest[li * DK_NEST_MAX + k - 1];
+        const int32_t* o = (const int32_t*)(H + L.o_noffs[k - 1]);
+        nl.depth = k; nl.list_def = L.list_def[k - 1];
+        nl.n_parent = hi - lo; nl.n_elem = o[hi] - o[lo]; nl.first = o[lo];
+        nl.parent_def = k == 1 ? c.row_def : H + L.o_ndef[k - 2] + lo;
+        nl.offs = o + lo;
+        const int64_t lo2 = o[lo], hi2 = o[hi];
+        lo = lo2; hi = hi2;
+      }
+    }
   }
   b->pub.file = w->file;
   b->pub.n_rows = nb;
@@ -6382,6 +6582,20 @@ extern "C" void dk_batch_release(dk_batch* pub) {
   r->outstanding--;
   delete b;
   reader_maybe_free(r, lk);
+}
+
+extern "C" int dk_batch_nest(const dk_batch* pub, int32_t col, int32_t depth, dk_batch_nest_level* out) {
+  if (!pub || !out) return fail("dk_batch_nest: null argument");
+  memset(out, 0, sizeof *out);
+  const dk_batch_impl* b = reinterpret_cast<const dk_batch_impl*>(pub);   // pub is the first member
+  if (col < 0 || col >= (int32_t)b->cols.size()) return fail("dk_batch_nest: bad column index");
+  const dk_batch_column& c = b->cols[col];
+  if (!c.present || c.max_rep <= 1) return fail("dk_batch_nest: column " + std::to_string(col) + " is not a nested leaf (max_rep <= 1)");
+  if (depth < 1 || depth > c.max_rep)
+    return fail("dk_batch_nest: depth " + std::to_string(depth) + " outside 1.." + std::to_string(c.max_rep));
+  if (b->nest.empty()) return fail("dk_batch_nest: this batch carries no nest levels");
+  *out = b->nest[(size_t)col * DK_NEST_MAX + depth - 1];
+  return 0;
 }
 
 extern "C" void dk_reader_close(dk_reader* r) {
@@ -6468,6 +6682,19 @@ static void replay_drop_scans(dk_replay* r) {
 
 // What dk_replay_scan_open and dk_replay_scan_open_rank share. First half, no device work: the
 // reader's sizes and its leaves resolved against the replay's projection.
+// a consumer whose batches cannot carry the structure of a nested leaf (max_rep >= 2, dk_nest.h)
+// refuses it by name when it opens: 1 (fail set) when leaf `pl` (pl < 0: any leaf) of the set is nested
+static int refuse_nested(const dk_parquet* p, int pl, const char* who) {
+  for (size_t fi = 0; fi < p->files.size(); fi++)
+    for (size_t li = 0; li < p->leaves.size(); li++) {
+      const int ci = p->colmap[fi][li];
+      if ((pl >= 0 && (int)li != pl) || ci < 0 || p->h_cols[ci].max_rep <= 1) continue;
+      return fail(std::string(who) + ": nested leaf " + p->leaves[li] + " (max_rep " + std::to_string(p->h_cols[ci].max_rep) +
+                  ") is not supported here: read it with readParquetFiles (dk_reader_*)");
+    }
+  return 0;
+}
+
 static int scan_open_leaves(dk_scan_reader* s, dk_replay* r, const char* const* leaves, int32_t n_leaves, int compact,
                             int32_t batch_rows, int32_t window_rows, const char* who) {
   s->eng = r->eng; s->rp = r;
@@ -6481,6 +6708,7 @@ static int scan_open_leaves(dk_scan_reader* s, dk_replay* r, const char* const* 
     if (r->ck) for (size_t k = 0; k < r->ck->leaves.size(); k++) if (r->ck->leaves[k] == leaves[i]) pl = (int)k;
     for (int k = 0; k < JL_N; k++) if (!strcmp(JSON_LEAVES[k], leaves[i])) jl = k;
     if (r->ck ? pl < 0 : jl < 0) return fail(std::string(who) + ": leaf not projected: " + leaves[i]);
+    if (r->ck && pl >= 0 && refuse_nested(r->ck, pl, who)) return 1;
     if (jl == JL_STATS && r->tail && !r->tail->with_stats) jl = -1;
     if (jl >= JL_RPATH) jl = -1;               // scan files are add rows
     s->leaves.push_back(leaves[i]); s->pleaf.push_back(pl); s->jleaf.push_back(jl);
@@ -7171,6 +7399,7 @@ extern "C" int dk_data_scan_open(dk_engine* e, const char* const* paths, int32_t
   for (auto& l : all) cl.push_back(l.c_str());
   if (parquet_open(e, paths, n_files, cl.data(), (int32_t)cl.size(), &groups, &s->dp, any_id ? ids.data() : nullptr)) return 1;
   dk_parquet* p = s->dp;
+  if (refuse_nested(p, -1, "dk_data_scan_open")) return 1;
   if (dk_parquet_decode(p) || dk_parquet_sync(p)) return 1;
   if (prog && install_part(s->dprog, *prog, DK_PROGRAM_DATA)) return 1;
   // per file: the filter's columns, the row-group map, the DV -> one selection byte per decoded row

@@ -16,12 +16,14 @@
 //   k_dlba_copy, k_dba_tail / k_dba_link / k_dba_expand   their bytes -> contiguous chars + key-path hashes
 //   k_string_copy       PLAIN string bytes -> contiguous chars + key-path hashes
 //   k_tile_decode       levels + values -> row_def / row_offs / entry_def / fixed / offs
+//   k_nest_count / k_nest_scan / k_nest_fill   nested leaves only (max_rep >= 2): per-depth offsets
 //   k_json_canon / k_table_insert / k_table_update / k_json_select   commit-tail keys
 //   k_probe_fast / k_probe_cand   checkpoint add rows: key hash, probe, verify, select
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
 #include "dk_device.h"
+#include "dk_nest.h"
 #include "dk_thrift.h"
 #include "dk_uri.h"
 
@@ -2534,6 +2536,158 @@ __global__ __launch_bounds__(NT) void k_tile_decode(const DChunk* __restrict__ c
     }
   }
   if (bad) { pages[T.page].status = PS_BAD_VALUES; atomicOr(&st->err_flags, E_PAGE); }
+}
+
+// --------------------------------------------------------------------------------------------
+// Nested leaves (max_rep = R >= 2, dk_nest.h): the structure between the row and the innermost list.
+// Launched per nested column over that column's level tiles, from the run tables of the sizing pass;
+// a set without a nested leaf launches none of them.
+//   k_nest_count   depth-k elements (k = 1..R-1) of each tile (depth 0 and R are k_tile_count's)
+//   k_nest_scan    one workgroup: exclusive scan over the column's tiles -> tile bases, n_k, and the
+//                  closing offs_k[n_{k-1}] = n_k once the outputs exist
+//   k_nest_fill    levels dealt to lanes strided as in k_tile_decode; one ballot per depth, wave
+//                  popcounts and an in-tile scan rank every level at every depth; the first level of
+//                  a depth-k element stores offs_{k+1} (its rank at depth k + 1) and def_k
+// --------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(NT) void k_nest_count(const DChunk* __restrict__ chunks, const DPage* __restrict__ pages,
+                                                   const DColumn* __restrict__ cols, const uint8_t* __restrict__ arena,
+                                                   const Seg* __restrict__ runs, const DTile* __restrict__ tiles,
+                                                   DNestTile* __restrict__ ntiles, const DNest* __restrict__ nest) {
+  const DNest N = *nest;
+  const DColumn col = cols[N.col];
+  const DTile T = tiles[col.first_tile + blockIdx.x];
+  DNestTile& O = ntiles[N.first_ntile + blockIdx.x];
+  const DPage pg = pages[T.page];
+  const int t = threadIdx.x;
+  __shared__ int lds[12];
+  int c1 = 0, c2 = 0, c3 = 0;
+  const int R = col.max_rep;
+  if (pg.status == PS_OK) {
+    const DChunk ck = chunks[pg.chunk];
+    const Layout L = page_layout(pg, ck, arena);
+    const int l_end = min(T.lvl0 + TL, pg.num_values);
+    const int a = T.lvl0 + t * LPT, b = min(a + LPT, l_end);
+    if (a < b) {
+      const int bwr = bit_width(ck.max_rep), bwd = bit_width(ck.max_def);
+      RunCur cr, cd;
+      cr.init(runs + pg.run_r, pg.nrun_r, a);
+      cd.init(runs + pg.run_d, pg.nrun_d, a);
+      for (int i = a; i < b; i++) {
+        const int rep = (int)cr.get(i, bwr, L.d, L.rep_e);
+        const int def = (int)cd.get(i, bwd, L.d, L.def_e);
+        c1 += nest_is_elem(rep, def, 1, col.list_def[0]);
+        c2 += R > 2 && nest_is_elem(rep, def, 2, col.list_def[1]);
+        c3 += R > 3 && nest_is_elem(rep, def, 3, col.list_def[2]);
+      }
+    }
+  }
+  int e1, e2, e3, t1, t2, t3;
+  block_scan3(c1, c2, c3, &e1, &e2, &e3, &t1, &t2, &t3, lds);
+  if (t == 0) { O.n[0] = t1; O.n[1] = t2; O.n[2] = t3; }
+}
+
+__global__ __launch_bounds__(NT) void k_nest_scan(const DColumn* __restrict__ cols, DNestTile* __restrict__ ntiles,
+                                                  DNest* __restrict__ nest) {
+  DNest& N = *nest;
+  const DColumn& c = cols[N.col];
+  const int nt = c.n_tiles, R = c.max_rep;
+  DNestTile* NTl = ntiles + N.first_ntile;
+  __shared__ int lds[12];
+  long long b1 = 0, b2 = 0, b3 = 0;
+  for (int p0 = 0; p0 < nt; p0 += NT) {
+    const int i = p0 + threadIdx.x;
+    int x = 0, y = 0, z = 0;
+    if (i < nt) { x = NTl[i].n[0]; y = NTl[i].n[1]; z = NTl[i].n[2]; }
+    int ex, ey, ez, tx, ty, tz;
+    block_scan3(x, y, z, &ex, &ey, &ez, &tx, &ty, &tz, lds);
+    if (i < nt) { NTl[i].base[0] = b1 + ex; NTl[i].base[1] = b2 + ey; NTl[i].base[2] = b3 + ez; }
+    b1 += tx; b2 += ty; b3 += tz;
+  }
+  if (threadIdx.x == 0) {
+    // (after k_tile_scan1 on the same stream: n_rows is the header's, n_entries the scan's)
+    const long long n[5] = {c.n_rows, R == 1 ? c.n_entries : b1, R == 2 ? c.n_entries : b2, R == 3 ? c.n_entries : b3,
+                            c.n_entries};
+    for (int k = 0; k <= R; k++) N.n[k] = n[k];
+    for (int k = 1; k <= R; k++)
+      if (N.offs[k - 1]) N.offs[k - 1][n[k - 1]] = n[k];
+  }
+}
+
+__global__ __launch_bounds__(NT) void k_nest_fill(const DChunk* __restrict__ chunks, const DPage* __restrict__ pages,
+                                                  const DColumn* __restrict__ cols, const uint8_t* __restrict__ arena,
+                                                  const Seg* __restrict__ runs, const DTile* __restrict__ tiles,
+                                                  const DNestTile* __restrict__ ntiles, const DNest* __restrict__ nest) {
+  constexpr int NW = NT / 64;
+  constexpr int ND = DK_NEST_MAX + 1;            // depths 0..R
+  const DNest N = *nest;
+  const DColumn col = cols[N.col];
+  const DTile T = tiles[col.first_tile + blockIdx.x];
+  const DNestTile NTl = ntiles[N.first_ntile + blockIdx.x];
+  const DPage pg = pages[T.page];
+  if (pg.status != PS_OK) return;
+  const DChunk ck = chunks[pg.chunk];
+  const Layout L = page_layout(pg, ck, arena);
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int l_end = min(T.lvl0 + TL, pg.num_values);
+  const int R = col.max_rep;
+  const int bwr = bit_width(ck.max_rep), bwd = bit_width(ck.max_def);
+  __shared__ int wcnt[ND][LPT][NW];              // per (depth, k, wave): elements
+  __shared__ int wbase[ND][LPT][NW];             // their exclusive scan in level order
+  __shared__ uint64_t wmask[ND][LPT][NW];        // and their ballots (40 masks held in SGPRs would spill)
+  // the tile's first element of every depth, within the column
+  long long base[ND];
+  base[0] = T.row_base;
+#pragma unroll
+  for (int k = 1; k < ND; k++) base[k] = k == R ? T.entry_base : k < R ? NTl.base[k - 1] : 0;
+  int df[LPT];
+  {
+    RunCur cr, cd;
+    const int i0 = T.lvl0 + t;
+    if (i0 < l_end) {
+      cr.init(runs + pg.run_r, pg.nrun_r, i0);
+      cd.init(runs + pg.run_d, pg.nrun_d, i0);
+    }
+#pragma unroll
+    for (int j = 0; j < LPT; j++) {
+      const int i = i0 + j * NT;
+      int rp = ND;                                // past the page's levels: no element at any depth
+      df[j] = -1;
+      if (i < l_end) {
+        rp = (int)cr.get(i, bwr, L.d, L.rep_e);
+        df[j] = (int)cd.get(i, bwd, L.d, L.def_e);
+      }
+#pragma unroll
+      for (int k = 0; k < ND; k++) {
+        const uint64_t m = __ballot(k <= R && nest_is_elem(rp, df[j], k, k ? col.list_def[k - 1] : 0));
+        if (lane == 0) { wcnt[k][j][wv] = __popcll(m); wmask[k][j][wv] = m; }
+      }
+    }
+  }
+  __syncthreads();
+  if (t < ND) {
+    int run = 0;
+    for (int j = 0; j < LPT; j++)
+      for (int q = 0; q < NW; q++) { wbase[t][j][q] = run; run += wcnt[t][j][q]; }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < LPT; j++) {
+    if (T.lvl0 + t + j * NT >= l_end) continue;
+    long long at[ND];                             // this level's exclusive rank at every depth
+    bool is[ND];
+#pragma unroll
+    for (int k = 0; k < ND; k++) {
+      const uint64_t m = wmask[k][j][wv];
+      at[k] = base[k] + wbase[k][j][wv] + lane_rank(m);
+      is[k] = (m >> lane) & 1;
+    }
+#pragma unroll
+    for (int k = 0; k < DK_NEST_MAX; k++) {
+      if (k >= R || !is[k]) continue;
+      gp(N.offs[k])[at[k]] = at[k + 1];
+      if (k >= 1) gp(N.def[k - 1])[at[k]] = (uint8_t)df[j];
+    }
+  }
 }
 
 // --------------------------------------------------------------------------------------------
@@ -5058,6 +5212,18 @@ void launch_tile_decode(const DChunk* c, DPage* p, const DColumn* cols, const ui
                         hipStream_t s) {
   if (ntiles)
     hipLaunchKernelGGL(k_tile_decode, dim3(ntiles), dim3(NT), 0, s, c, p, cols, arena, pos, dbp, runs, t, tile0, st);
+}
+// one nested column (nest: its DNest in device memory; ntiles: the column's level tiles)
+void launch_nest_count(const DChunk* c, const DPage* p, const DColumn* cols, const uint8_t* arena, const Seg* runs,
+                       const DTile* t, DNestTile* nt, DNest* nest, int ntiles, hipStream_t s) {
+  if (ntiles) hipLaunchKernelGGL(k_nest_count, dim3(ntiles), dim3(NT), 0, s, c, p, cols, arena, runs, t, nt, nest);
+}
+void launch_nest_scan(const DColumn* cols, DNestTile* nt, DNest* nest, hipStream_t s) {
+  hipLaunchKernelGGL(k_nest_scan, dim3(1), dim3(NT), 0, s, cols, nt, nest);
+}
+void launch_nest_fill(const DChunk* c, const DPage* p, const DColumn* cols, const uint8_t* arena, const Seg* runs,
+                      const DTile* t, const DNestTile* nt, const DNest* nest, int ntiles, hipStream_t s) {
+  if (ntiles) hipLaunchKernelGGL(k_nest_fill, dim3(ntiles), dim3(NT), 0, s, c, p, cols, arena, runs, t, nt, nest);
 }
 void launch_delta_decode(const DChunk* c, DPage* p, int n, const uint8_t* arena, long long* dbp, hipStream_t s) {
   if (n) hipLaunchKernelGGL(k_delta_decode, dim3(n), dim3(NT), 0, s, c, p, arena, dbp);

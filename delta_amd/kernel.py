@@ -27,9 +27,10 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (MAX_LEAF_DEPTH, BatchReader, Column, DkError, Handle, check, dk_batch, dk_column, dk_config,
-                   dk_data_options, dk_dv_descriptor, dk_rank_scan_options, dk_read_options, dk_rg_filter,
-                   dk_scan_options, lib)
+from ._lib import (MAX_LEAF_DEPTH, BatchReader, Column, DkError, Handle, check, dk_batch, dk_batch_nest_level, dk_column,
+                   dk_config, dk_data_options, dk_dv_descriptor, dk_nest_level, dk_rank_scan_options, dk_read_options,
+                   dk_rg_filter, dk_scan_options, lib)
+from ._lib import _arr as _lib_arr, _view as _lib_view
 
 ADD_LEAVES = ["add.path", "add.partitionValues.key_value.key", "add.partitionValues.key_value.value",
               "add.size", "add.modificationTime", "add.dataChange",
@@ -180,8 +181,26 @@ class ParquetSet(Handle):
     def column(self, file_idx, leaf, copy=True) -> Column:
         """copy=False: a view of the library's pinned mirror, valid until the next decode / close."""
         c = dk_column()
-        check(lib().dk_parquet_column(self._h, file_idx, self.leaves.index(leaf), C.byref(c)))
-        return Column(c, leaf, copy)
+        li = self.leaves.index(leaf)
+        check(lib().dk_parquet_column(self._h, file_idx, li, C.byref(c)))
+        col = Column(c, leaf, copy)
+        arr = _lib_arr if copy else _lib_view
+        for depth in range(1, c.max_rep + 1 if c.present and c.max_rep > 1 else 0):
+            lv = dk_nest_level()
+            check(lib().dk_parquet_column_nest(self._h, file_idx, li, depth, C.byref(lv)))
+            col.nest.append((lv.list_def, arr(lv.parent_def, lv.n_parent, np.uint8), arr(lv.offs, lv.n_parent + 1, np.int64)))
+        return col
+
+    def kernel_stats(self):
+        """{kernel: (mean event us, launches)} of the set's decode kernels (engine timing=True)."""
+        out = {}
+        for i in range(64):
+            name, avg, cnt = C.c_char_p(), C.c_double(), C.c_int64()
+            if lib().dk_parquet_kernel_stats(self._h, i, C.byref(name), C.byref(avg), C.byref(cnt)) != 0:
+                break
+            if cnt.value:
+                out[name.value.decode()] = (avg.value, cnt.value)
+        return out
 
     def first_row(self, file_idx, leaf, min_def=1):
         """Index of the first row whose definition level is >= min_def, or -1 (device scan)."""
@@ -257,10 +276,20 @@ class BatchColumn:
     """One leaf of a ColumnarBatch, copied out of the batch's pinned buffers. Offsets are rebased to the
     batch (row_offs / offs start at 0), so the layout equals a dk_column slice of the same rows."""
 
-    def __init__(self, c, n_rows, path):
+    def __init__(self, c, n_rows, path, batch=None, index=0):
+        """batch, index: the dk_batch and the column's index in it, for the nest levels of a nested
+        leaf (dk_batch_nest); without them `nest` stays empty."""
         self.path = path
         self.present = bool(c.present)
         self.n_rows = n_rows
+        # nested leaf (max_rep >= 2): (list_def, parent_def, offs) per depth, offsets rebased to the batch
+        self.nest = []
+        if batch is not None and c.present and c.max_rep > 1:
+            for depth in range(1, c.max_rep + 1):
+                lv = dk_batch_nest_level()
+                check(lib().dk_batch_nest(C.byref(batch), index, depth, C.byref(lv)))
+                o = _np_view(lv.offs, lv.n_parent + 1, np.int32).astype(np.int64)
+                self.nest.append((lv.list_def, _np_view(lv.parent_def, lv.n_parent, np.uint8).copy(), o - lv.first))
         self.phys, self.width, self.max_def, self.max_rep, self.rep_def = c.phys, c.width, c.max_def, c.max_rep, c.rep_def
         self.row_def = _np_view(c.row_def, n_rows, np.uint8).copy()
         self.row_offs = self.entry_def = self.fixed = self.offs = self.chars = self.validity = None
@@ -291,7 +320,7 @@ class ColumnarBatch:
     def __init__(self, b: dk_batch, leaves, want_row_index):
         self.file = b.file
         self.n_rows = b.n_rows
-        self.columns = {leaf: BatchColumn(b.cols[i], b.n_rows, leaf) for i, leaf in enumerate(leaves)}
+        self.columns = {leaf: BatchColumn(b.cols[i], b.n_rows, leaf, b, i) for i, leaf in enumerate(leaves)}
         self.row_index = _np_view(b.row_index, b.n_rows, np.int64).copy() if want_row_index else None
 
 

@@ -141,6 +141,26 @@ int64_t dk_parquet_num_rows(dk_parquet* p, int32_t file);
  * The first request for a leaf queues that leaf's D2H copy for this file and every later file of
  * the set (a scan consumer reads the same leaves of every batch); each request waits for its file. */
 int  dk_parquet_column(dk_parquet* p, int32_t file, int32_t leaf, dk_column* out);
+/* Nested leaves: a leaf under R = max_rep >= 2 repeated nodes (array<array<..>>, map<.., array<..>>,
+ * array<struct<.., array<..>>>; R <= 4). dk_column is the innermost level of such a leaf: n_entries,
+ * entry_def and the value arrays are dense over the depth-R elements, rep_def is the definition
+ * level of the R-th repeated node and row_offs[row] the row's first depth-R element. The structure
+ * between the row and that level is one nest level per depth k = 1..R (Arrow's ListArray nesting):
+ *   offs[j], j <= n_parent   depth-k elements before the j-th depth-(k-1) element (depth 0: the rows);
+ *                            offs[n_parent] = n_elem. offs of depth R indexes the value arrays.
+ *   parent_def[j]            definition level at that parent's first level (depth 1: row_def)
+ *   list_def                 definition level of the k-th repeated node: parent j holds elements when
+ *                            parent_def[j] >= list_def, its list is empty when parent_def[j] ==
+ *                            list_def - 1, and the list or an ancestor of it is null below that
+ * Library-owned pinned host memory with the lifetime of dk_parquet_column's arrays. Fails for depth
+ * outside 1..max_rep and for a leaf with max_rep <= 1. */
+typedef struct dk_nest_level {
+  int32_t depth, list_def;
+  int64_t n_parent, n_elem;
+  const uint8_t* parent_def;     /* [n_parent] */
+  const int64_t* offs;           /* [n_parent + 1] */
+} dk_nest_level;
+int  dk_parquet_column_nest(dk_parquet* p, int32_t file, int32_t leaf, int32_t depth, dk_nest_level* out);
 /* Snapshot-load P&M pass (LogReplay.loadTableProtocolAndMetadata, internal/replay/LogReplay.java:
  * 220-314, which takes the first row whose protocol / metaData is non-null): index of the first row
  * of a decoded column with definition level >= min_def, found on the device; -1 when none. */
@@ -173,6 +193,9 @@ int  dk_parquet_traffic(dk_parquet* p, int64_t* bytes_read, int64_t* bytes_writt
 int  dk_parquet_snappy_serial(dk_parquet* p, int64_t* n_pages, int64_t* n_serial);
 /* algorithmic bytes one launch of a decode kernel must move ("k_string_copy", "k_tile_decode") */
 int  dk_parquet_kernel_traffic(dk_parquet* p, const char* kernel, int64_t* bytes_read, int64_t* bytes_written);
+/* timer slot i of the set's decode kernels (DK_FLAG_TIMING, after dk_parquet_sync): its name, mean
+ * event time and launch count; non-zero past the last slot */
+int  dk_parquet_kernel_stats(dk_parquet* p, int32_t i, const char** name, double* avg_us, int64_t* count);
 void dk_parquet_close(dk_parquet* p);
 
 /* ---- Streaming ParquetHandler.readParquetFiles (ParquetHandler.java:64-68) ----
@@ -230,6 +253,20 @@ int  dk_reader_next(dk_reader* r, dk_batch** out);
 int64_t dk_reader_num_rows(dk_reader* r, int32_t file);   /* rows the reader yields for a file */
 void dk_batch_release(dk_batch* b);
 void dk_reader_close(dk_reader* r);
+/* One nest level of a nested leaf (max_rep >= 2, see dk_nest_level) of a dk_reader batch, in the batch
+ * convention: the depth-k arrays are shared by the batches of one transfer window, offs holds absolute
+ * indices into the window's depth-k arrays (depth max_rep: the value-indexed arrays, offs[0] ==
+ * value_offset) and first is the batch's first depth-k element. parent_def and offs start at the
+ * batch's first depth-(k-1) element (depth 1: its first row). Valid until dk_batch_release. Fails
+ * for depth outside 1..max_rep, a leaf with max_rep <= 1 and a batch of another reader kind. */
+typedef struct dk_batch_nest_level {
+  int32_t depth, list_def;
+  int64_t n_parent, n_elem;      /* depth-(k-1) and depth-k elements of the batch */
+  int64_t first;                 /* == offs[0] */
+  const uint8_t* parent_def;     /* [n_parent] */
+  const int32_t* offs;           /* [n_parent + 1] */
+} dk_batch_nest_level;
+int  dk_batch_nest(const dk_batch* b, int32_t col, int32_t depth, dk_batch_nest_level* out);
 
 /* ---- Deletion vectors (Scan.transformPhysicalData's DV load, Scan.java:176-199) ----
  * Each descriptor is a scan file's add.deletionVector. A DV with cardinality 0 is empty and not read;
